@@ -15,11 +15,17 @@ of the subtree roots are exchanged over RCCL, the top is swept redundantly, each
 Gram matrix of its blkval ranges and one all-reduce of the m x m matrix H completes it; potrf / potrs of H
 are replicated.  (--shard columns selects the simpler column sharding of H.)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` for the
-dominant kernel (HIP-event timing inside the timed region), `cpu_baseline` (the CPU oracle timed on this
-host, median of three repeats), `back_solve` (the solve_ sub-rate of SURVEY 8d: two Hessians + potrs on
-the factored system) and, for the default N = 1 run, `secondary`: the GPU-only figures of BASELINE.json's
-configs 2, 3 and 4 (dense4096, arrow, maxcut; a few steps each, no CPU leg; --no-secondary skips them).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps
+steps, writes their outputs if --dump-outputs is given and prints the headline figure (`value`, `ms_per_step`, ...).
+With --full the line also carries `roofline` for the dominant kernel (HIP-event timing inside the timed region),
+`stages`, `cpu_baseline` (the CPU oracle timed on this host, median of three repeats), `back_solve` (the solve_
+sub-rate of SURVEY 8d: two Hessians + potrs on the factored system), `sharded_vs_single` (N > 1) and, for the
+default N = 1 run, `secondary`: the figures of BASELINE.json's other configurations (dense4096, arrow, maxcut, ...;
+a few steps each; --no-secondary skips them).
+
+--dump-outputs DIR: after the timed steps, what the last of them computed -- x and y of the search direction and the
+factor L and projected inverse Y of the scaling point, each on the entries of the sparsity pattern -- as DIR/<name>.npy
+in float64, at most 64 MiB in all (a fixed, seeded sample of the entries of a larger output).
 """
 import argparse
 import ctypes
@@ -37,6 +43,30 @@ sys.path.insert(0, ROOT)
 PMC_FILE = "r05_pmc_%s.json"       # per workload key: tools/pmc_step.sh (three rocprofv3 --pmc passes; one step = one period of the launch sequence)
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 achievable)
 FP64_PEAK_TFLOPS = 78.6   # vendor fp64 vector = matrix peak
+DUMP_BUDGET = 64 << 20    # bytes: all files of --dump-outputs together
+# keys of the result line that only --full measures
+FULL_ONLY = ("roofline", "stages", "cpu_baseline", "back_solve", "sharded_vs_single", "kernel_ms_per_step")
+
+
+def write_outputs(path, arrays, budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: every array as <path>/<name>.npy in float64.  When together they would exceed `budget` bytes, the
+    longest ones are cut to a fixed, seeded sample of their entries (the same positions in every run with the same
+    arguments, in ascending order).  Returns {name: [entries written, entries computed]}."""
+    flat = {k: np.ascontiguousarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    room = (budget - 4096 * len(flat)) // 8          # entries, less room for the .npy headers
+    caps = {}
+    order = sorted(flat, key=lambda k: flat[k].size)
+    for i, k in enumerate(order):                    # shortest first: an array within its share is written whole
+        caps[k] = min(flat[k].size, room // (len(order) - i))
+        room -= caps[k]
+    os.makedirs(path, exist_ok=True)
+    info = {}
+    for k, v in flat.items():
+        if caps[k] < v.size:
+            v = v[np.sort(np.random.default_rng(seed).choice(v.size, caps[k], replace=False))]
+        np.save(os.path.join(path, k + ".npy"), v)
+        info[k] = [int(v.size), int(flat[k].size)]
+    return info
 
 
 def build_workload(name, seed=0):
@@ -604,7 +634,7 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
         for _ in range(max(1, min(warmup, 2))):
             step()
         barrier()
-    prof = not args.no_profile
+    prof = args.full and not args.no_profile
     back_solve = None
     nk = int(lib.csp_profile_kinds())
     names = [lib.csp_profile_kernel_name(i).decode() for i in range(nk)]
@@ -660,6 +690,13 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
     ms_per_step = 1e3 * elapsed / steps
     if lazy:
         chordal.lazy_status(symb, False)
+    dumped = None
+    if primary and args.dump_outputs:
+        # what the last timed step left for its caller, on the entries of the sparsity pattern (the spmatrix export)
+        pos = torch.from_numpy(symb.ccs_to_blk().astype(np.int64)).to(dev)
+        dumped = write_outputs(args.dump_outputs, {"x": bx.blkval[pos].cpu().numpy(), "y": by.cpu().numpy(),
+                                                   "cholesky_factor": L.blkval[pos].cpu().numpy(),
+                                                   "projected_inverse": Y.blkval[pos].cpu().numpy()})
 
     # ---------------- roofline of the dominant kernel (HIP events on its launches inside the timed region) ------
     roofline = None
@@ -683,7 +720,7 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
     # ---------------- back-solve sub-rate: solve_ alone on the factored system of the last step ------
     # two Hessian applications + Amap / Aadj + potrs (solvers.py:506-541); an interior-point iteration issues ~9 of them
     # per factorisation (solvers.py:907-913, 1035-1044)
-    if world == 1 and part is None and args.kktsolver == "chol" and not args.no_back_solve:
+    if world == 1 and part is None and args.kktsolver == "chol" and args.full and not args.no_back_solve:
         nbs = 20
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         for it in range(nbs + 2):
@@ -702,7 +739,7 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
     # ---------------- N > 1: the sharded step against the plain single-rank step on rank 0's device (untimed) --------
     # y is replicated, x was left sharded: compared on the cliques rank 0 owns and the top
     sharded_check = None
-    if (world > 1 or force_sharded) and part is not None and rank == 0 and primary and args.kktsolver == "chol" and not args.no_check:
+    if (world > 1 or force_sharded) and part is not None and rank == 0 and primary and args.kktsolver == "chol" and args.full and not args.no_check:
         try:
             own = kkt._own_mask.bool().clone()
             for a_, b_ in part.top_ranges:
@@ -843,6 +880,11 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
             # calibration pass that precedes them (events around every launch)
             "kernel_ms_per_step": {k: round(v[0], 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1][0])},
         }
+        if not args.full:
+            for k in FULL_ONLY:
+                del out[k]
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "dtype": "f64", "entries_written_of_computed": dumped}
         result = out
     # release the device context of this workload before the next one is built
     if lazy:
@@ -854,7 +896,7 @@ def run_workload(args, workload, steps, warmup, want_cpu, primary, env):
     return result
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -880,7 +922,24 @@ def main():
     ap.add_argument("--cpu-repeats", type=int, default=3, help="repeats of the CPU baseline (the median is reported)")
     ap.add_argument("--no-profile", action="store_true", help="skip HIP-event kernel timing")
     ap.add_argument("--verbose", action="store_true")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel HIP-event times and the roofline "
+                         "of the dominant kernel, the stage split, back_solve, the CPU baseline with its comparison against the oracle, "
+                         "the sharded-vs-single check (N > 1) and the secondary workloads (the --no-* options above switch them off "
+                         "one by one).  Off: set-up, warm-up, the timed steps and the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (x, y, cholesky_factor, projected_inverse on the "
+                         "entries of the sparsity pattern) as DIR/<name>.npy, float64, at most 64 MiB in all; one GPU")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("SMCP_BENCH_FORCE_SHARDED") == "1"):
+        ap.error("--dump-outputs: one GPU, unsharded (x is left sharded over the ranks)")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world_env = os.environ.get("WORLD_SIZE")
     if args.gpus > 1 and world_env is None:
@@ -933,10 +992,10 @@ def main():
     lib = _lib.lib()
 
     env = {"world": world, "rank": rank, "dev": dev, "lib": lib, "force_sharded": force_sharded}
-    out = run_workload(args, args.workload, args.steps, args.warmup, None if args.no_cpu else "full", True, env)
-    # BASELINE.json's other single-GPU configurations, GPU only: config 2 (one dense 4096 front), config 3 (block-arrow),
+    out = run_workload(args, args.workload, args.steps, args.warmup, None if args.no_cpu or not args.full else "full", True, env)
+    # --full: BASELINE.json's other single-GPU configurations: config 2 (one dense 4096 front), config 3 (block-arrow),
     # config 4 (max-cut, column-sparse constraints) -- a few steps each after the headline measurement
-    if world == 1 and not force_sharded and args.workload == "synth50k" and not args.no_secondary and args.kktsolver == "chol":
+    if world == 1 and not force_sharded and args.workload == "synth50k" and args.full and not args.no_secondary and args.kktsolver == "chol":
         sec = {}
         for name in ("dense4096", "arrow", "maxcut", "synth50k_dense", "synth50k_trace", "band200"):
             try:

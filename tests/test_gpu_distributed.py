@@ -576,14 +576,14 @@ def test_one_launch_cholesky_beside_itself_in_three_processes(n, nproc):
 def test_bench_self_launch_two_ranks_gloo():
     """The code path the driver's scaling run takes -- `python bench.py --gpus N` starting its own ranks (self_launch) and the
     N > 1 branch of the timed protocol -- with N = 2 ranks sharing the one GPU over gloo: one JSON line, n_gpus, the partition
-    named, and the sharded search direction equal to the single-rank one (bench.py's own untimed check)."""
+    named, and the sharded search direction equal to the single-rank one (bench.py's own untimed check, part of --full)."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SMCP_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
                         "--no-secondary", "--tune-placement", "2"], env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -3,11 +3,12 @@
 # (each setting twice, interleaved; prints ms_per_step, the stage times and the kernels that moved)
 set -o pipefail
 SW=$1; VALS=${2:-"0 1"}; WL=${3:-synth50k}; STEPS=${4:-20}
-mkdir -p gpurun_out/ab
+out=${OUT:-out}
+mkdir -p $out/ab
 for rep in $(seq 1 ${REPS:-2}); do
   for v in $VALS; do
-    env $SW=$v python3 bench.py --workload $WL --steps $STEPS --warmup 3 --no-cpu --no-secondary > gpurun_out/ab/${SW}_${v}_${rep}.json 2> gpurun_out/ab/${SW}_${v}_${rep}.err || { echo "bench failed ($SW=$v)"; tail -5 gpurun_out/ab/${SW}_${v}_${rep}.err; exit 1; }
-    python3 - gpurun_out/ab/${SW}_${v}_${rep}.json $SW $v <<'PY'
+    env $SW=$v python3 bench.py --full --workload $WL --steps $STEPS --warmup 3 --no-cpu --no-secondary > $out/ab/${SW}_${v}_${rep}.json 2> $out/ab/${SW}_${v}_${rep}.err || { echo "bench failed ($SW=$v)"; tail -5 $out/ab/${SW}_${v}_${rep}.err; exit 1; }
+    python3 - $out/ab/${SW}_${v}_${rep}.json $SW $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 k = d.get("kernel_ms_per_step") or {}

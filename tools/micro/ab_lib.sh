@@ -5,7 +5,7 @@ cp smcp_amd/libsmcp_amd.so /tmp/orig.so
 for rep in 1 2; do
 for v in orig nw12 nw16; do
   if [ $v = orig ]; then cp /tmp/orig.so smcp_amd/libsmcp_amd.so; else cp tools/micro/bin/libsmcp_$v.so smcp_amd/libsmcp_amd.so; fi
-  python3 bench.py --workload synth50k --steps 20 --warmup 3 --no-cpu --no-secondary > /tmp/o.json 2>/tmp/o.err
+  python3 bench.py --full --workload synth50k --steps 20 --warmup 3 --no-cpu --no-secondary > /tmp/o.json 2>/tmp/o.err
   python3 - $v <<'PY'
 import json, sys
 d = json.loads(open('/tmp/o.json').read().strip().splitlines()[-1])

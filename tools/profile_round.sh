@@ -6,8 +6,8 @@ cd $GRAFT_REPO_ROOT
 export ROUND=${ROUND:-r04}
 out=gpurun_out/prof_$ROUND
 rm -rf $out; mkdir -p $out
-python3 bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err && \
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python3 bench.py --no-secondary --steps 5 --no-cpu --no-back-solve > $out/stats.log 2>&1 && \
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err && \
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python3 bench.py --full --no-secondary --steps 5 --no-cpu --no-back-solve > $out/stats.log 2>&1 && \
 cp $out/stats/*kernel_stats.csv $out/kernel_stats.csv && \
 bash tools/hbm_traffic.sh > $out/hbm.log 2>&1 && \
 bash tools/pmc_mfma.sh > $out/mfma.log 2>&1 && \

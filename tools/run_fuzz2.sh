@@ -7,4 +7,4 @@ timeout -k 10 300 python3 tools/fuzz_sharded.py 60 172000 3 > gpurun_out/fuzz2_s
 timeout -k 10 300 python3 tools/fuzz_sharded.py 60 173000 4 > gpurun_out/fuzz2_sharded4.log 2>&1; echo "fuzz_sharded(4) rc=$?"; tail -1 gpurun_out/fuzz2_sharded4.log
 timeout -k 10 900 python3 tools/fuzz_ipm.py 48 174000 > gpurun_out/fuzz2_ipm.log 2>&1; echo "fuzz_ipm rc=$?"; tail -1 gpurun_out/fuzz2_ipm.log
 timeout -k 10 300 python3 tools/fuzz_maxcut.py > gpurun_out/fuzz2_maxcut.log 2>&1; echo "fuzz_maxcut rc=$?"; tail -2 gpurun_out/fuzz2_maxcut.log
-python3 bench.py --workload maxcut --steps 10 --warmup 3 --no-cpu --no-secondary 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('maxcut', d['value'], d['roofline'])"
+python3 bench.py --full --workload maxcut --steps 10 --warmup 3 --no-cpu --no-secondary 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('maxcut', d['value'], d['roofline'])"
