@@ -70,8 +70,11 @@ enum {
   CSP_Q_ROWIDX = 6, CSP_Q_SEPPTR = 7, CSP_Q_RELIDX = 8, CSP_Q_BLKPTR = 9, CSP_Q_UPDPTR = 10,
   CSP_Q_CHPTR = 11, CSP_Q_CHIDX = 12, CSP_Q_LEVPTR = 13, CSP_Q_LEVIDX = 14, CSP_Q_CCSPTR = 15,
   CSP_Q_SNODE = 16,
-  CSP_Q_FAMILY = 17  /* nsn, after csp_device_init: 2 = small front swept together with its childless children in one
+  CSP_Q_FAMILY = 17, /* nsn, after csp_device_init: 2 = small front swept together with its childless children in one
                         workgroup (family kernel of the sparse-input Schur sweeps), 1 = such a child, 0 = neither */
+  CSP_Q_MRC_CLAMPED = 18  /* 1 value: cliques of the last csp_mrcompletion on this context whose Schur-complement factor had
+                             more pivots above the threshold than the r columns left room for (0 when r came from
+                             csp_mrcompletion_rank with the same X and tol, up to rounding) */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -120,6 +123,19 @@ int csp_hessian(csp_ctx* ctx, const double* L, const double* Y, double* U, int64
  * with rows in the permuted (symbolic) order; trans 0: L^-1 B, 1: L^-T B. */
 int csp_trsm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb, int trans,
              void* stream);
+/* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
+ * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
+ * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */
+int csp_mrcompletion_rank(csp_ctx* ctx, const double* blkval, double tol, int64_t* r, void* stream);
+/* chompack.mrcompletion(X), pass 2: Y (n x r, row i at Y + i*ldY, rows in the permuted order) with P_V(Y Y^T) = X, for
+ * the r of csp_mrcompletion_rank (same X and tol).  Top-down over the clique tree: per clique a column-pivoted QR of
+ * Y_A^T, a triangular solve and the pivoted Cholesky factor of the Schur complement.  Deterministic; synchronises. */
+int csp_mrcompletion(csp_ctx* ctx, const double* blkval, double tol, int64_t r, double* Y, int64_t ldY, void* stream);
+/* Goemans-Williamson rounding of a Y of csp_mrcompletion (device arrays): for trial t, s[t*n + i] = sign(Y_i . g_t) with
+ * 0 -> +1 (g_t = G + t*r), and cut[t] = sum of w[e] over the edges (ei[e], ej[e]) (permuted indices) whose ends get
+ * different signs, summed in a fixed order. */
+int csp_maxcut_cuts(csp_ctx* ctx, const double* Y, int64_t ldY, int64_t r, int64_t trials, const double* G, int64_t nedges,
+                    const int64_t* ei, const int64_t* ej, const double* w, int8_t* s, double* cut, void* stream);
 /* chompack.dot(X, Y) = tr(XY) on V (solvers.py:399,836,...); result written to *out (host). */
 int csp_dot(csp_ctx* ctx, const double* X, const double* Y, double* out, void* stream);
 /* sum(log(X.diag())) (solvers.py:395,925,934); *out host. */

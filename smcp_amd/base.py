@@ -414,14 +414,10 @@ class mtxnorm_SDP(SDP):
         self._blockstruct = [n]
 
 
-def completion(X):
-    """Maximum-determinant positive definite completion of the sparse symmetric matrix X (scipy sparse, either
-    triangle or both), returned as a dense numpy array; ArithmeticError if X has no positive definite completion.
-    Counterpart of smcp.completion (base.py:952-973): embed the pattern (perfect elimination order if it is chordal,
-    minimum degree otherwise), chompack-level completion -> factor L of the inverse, then Z = (L L^T)^-1 by two
-    supernodal triangular solves with the identity."""
+def _on_pattern(X):
+    """(cspmatrix of X, device) for the sparse symmetric X (scipy sparse, either triangle or both) on its pattern, embedded
+    as smcp.completion does (base.py:952-973): perfect elimination order if it is chordal, minimum degree otherwise."""
     import torch
-    from . import chordal
     from .cspmatrix import cspmatrix
     from .symbolic import Symbolic, maxcardsearch, mindegree
     X = sp.csc_matrix(X)
@@ -432,7 +428,20 @@ def completion(X):
     if symb.fill > 0:
         symb = Symbolic(pat, mindegree(pat))
     dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    L = cspmatrix.from_entries(symb, Xl.row, Xl.col, Xl.data, device=dev)
+    return cspmatrix.from_entries(symb, Xl.row, Xl.col, Xl.data, device=dev), dev
+
+
+def completion(X):
+    """Maximum-determinant positive definite completion of the sparse symmetric matrix X (scipy sparse, either
+    triangle or both), returned as a dense numpy array; ArithmeticError if X has no positive definite completion.
+    Counterpart of smcp.completion (base.py:952-973): embed the pattern (perfect elimination order if it is chordal,
+    minimum degree otherwise), chompack-level completion -> factor L of the inverse, then Z = (L L^T)^-1 by two
+    supernodal triangular solves with the identity."""
+    import torch
+    from . import chordal
+    n = sp.csc_matrix(X).shape[0]
+    L, dev = _on_pattern(X)
+    symb = L.symb
     chordal.completion(L)
     B = torch.eye(n, dtype=torch.float64, device=dev)          # rows = right-hand sides, PERMUTED coordinates
     chordal.trsm(L, B)
@@ -441,6 +450,53 @@ def completion(X):
     ip = np.asarray(symb.ip)
     Z = Z[np.ix_(ip, ip)]
     return 0.5 * (Z + Z.T)
+
+
+def mrcompletion(X, tol=1e-12):
+    """Minimum-rank positive semidefinite completion of the sparse symmetric X (scipy sparse, either triangle or both):
+    Y (numpy, n x r, ORIGINAL order) with (Y Y^T)_ij = X_ij on the pattern of X, r = the largest numerical rank of a
+    clique block (chompack.mrcompletion; smcp_amd.chordal.mrcompletion for the rank and tolerance semantics).  The
+    pattern is embedded as in completion().  ArithmeticError if X has no positive semidefinite completion."""
+    Y, symb = _mrcompletion(X, tol)
+    return Y.cpu().numpy()[np.asarray(symb.ip)]
+
+
+def _mrcompletion(X, tol):
+    """(Y on the device in the permuted order, its Symbolic)"""
+    from . import chordal
+    L, _ = _on_pattern(X)
+    return chordal.mrcompletion(L, tol), L.symb
+
+
+def maxcut_round(P, X, trials=64, seed=0, tol=1e-8):
+    """Goemans-Williamson rounding of a max-cut relaxation (maxcut_SDP: C = -(Diag(W 1) - W) / 4) at its solution X
+    (scipy sparse, e.g. sol['x']): Y = mrcompletion(X, tol), `trials` Gaussian directions g_t drawn with numpy's
+    default_rng(seed), s_t = sign(Y g_t) (0 -> +1) and the cut weight of every s_t on the device (csp_maxcut_cuts).
+    Returns (best cut value, s) with s in {-1, +1}^n (float64, original order); the cut of s is -<C, s s^T>, that is
+    the sum of the edge weights W_ij = 4 C_ij (i > j) whose ends get different signs.  The first of equal best trials wins."""
+    import ctypes
+    import torch
+    from . import _lib, chordal
+    from .cspmatrix import _stream
+    Y, symb = _mrcompletion(X, tol)
+    n, r = Y.shape
+    C = sp.tril(sp.csc_matrix(P.get_A(0)), -1).tocoo()
+    ip = np.asarray(symb.ip)
+    keep = C.data != 0.0
+    ei = torch.from_numpy(ip[C.row[keep]].astype(np.int64)).to(Y.device)
+    ej = torch.from_numpy(ip[C.col[keep]].astype(np.int64)).to(Y.device)
+    w = torch.from_numpy(4.0 * C.data[keep].astype(np.float64)).to(Y.device)
+    if r == 0:                 # X = 0: every direction gives s = +1, the empty cut
+        return 0.0, np.ones(n)
+    G = torch.from_numpy(np.random.default_rng(seed).standard_normal((trials, r))).to(Y.device)
+    s = torch.empty((trials, n), dtype=torch.int8, device=Y.device)
+    cut = torch.empty(trials, dtype=torch.float64, device=Y.device)
+    chordal._chk(_lib.lib().csp_maxcut_cuts(symb.handle, Y.data_ptr(), r, r, trials, G.data_ptr(), int(w.numel()),
+                                            ei.data_ptr(), ej.data_ptr(), w.data_ptr(), s.data_ptr(), cut.data_ptr(),
+                                            _stream()), "maxcut_round")
+    cuts = cut.cpu().numpy()
+    t = int(np.argmax(cuts))
+    return float(cuts[t]), s[t].cpu().numpy().astype(np.float64)[ip]
 
 
 class pattern_SDP(SDP):

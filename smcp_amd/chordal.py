@@ -130,6 +130,23 @@ def completion(X):
         note_cache(X.symb, X)
 
 
+def mrcompletion(X, tol=1e-12):
+    """chompack.mrcompletion(X): Y (n x r, float64 device tensor, rows in the PERMUTED order) with P_V(Y Y^T) = X, where
+    r is the largest numerical rank of a clique block X_gg (pivots of a diagonally pivoted Cholesky above
+    tol * max diag(X_gg)).  X is not changed.  ArithmeticError (naming the clique) when a clique block has a pivot below
+    -tol * max diag(X_gg): X has no positive semidefinite completion."""
+    symb = X.symb
+    _ensure(symb)
+    L = _lib.lib()
+    r = ctypes.c_int64(0)
+    _chk(L.csp_mrcompletion_rank(symb.handle, X.blkval.data_ptr(), float(tol), ctypes.byref(r), _stream()), "mrcompletion")
+    Y = torch.zeros((symb.n, r.value), dtype=torch.float64, device=X.blkval.device)
+    if r.value:
+        _chk(L.csp_mrcompletion(symb.handle, X.blkval.data_ptr(), float(tol), r.value, Y.data_ptr(), r.value, _stream()),
+             "mrcompletion")
+    return Y
+
+
 _ADJ = {False: 0, True: 1, None: 2}
 
 

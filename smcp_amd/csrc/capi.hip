@@ -29,6 +29,7 @@
 #include "front_leafgram.hip"
 #include "front_famt.hip"
 #include "front_flow.hip"
+#include "front_mrc.hip"
 
 using namespace smcp;
 
@@ -59,6 +60,7 @@ enum {
   KID_completion_mfma, KID_completion_mfma_hbm, KID_lf_copy_an, KID_lf_ri_an, KID_lf_dinv1, KID_lf_dinv2,
   KID_lf_uinv1, KID_lf_uinv2, KID_lf_completion, KID_hess_up_n16, KID_llt_mfma, KID_llt_mfma_hbm, KID_lf_llt,
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
+  KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -76,7 +78,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_hess_up_inv_mfma<false>", "k_completion_mfma<true>", "k_completion_mfma<false>", "k_lf_copy_an", "k_lf_ri_an",
   "k_lf_dinv1", "k_lf_dinv2", "k_lf_uinv1", "k_lf_uinv2", "k_lf_completion", "k_hess_up_n16",
   "k_llt_mfma<true>", "k_llt_mfma<false>", "k_lf_llt", "k_hess_up_fam",
-  "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow"};
+  "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
+  "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2127,7 +2130,8 @@ void csp_symbolic_destroy(csp_ctx* c) {
     hipSetDevice(D.device);
     void* ptrs[] = {D.lfsp_skip, D.famt_skip, D.both_skip, D.trsm_x, D.fp, D.fp_bad, D.gsl_start, D.gsl_len, D.lg_list, D.lg_slot, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.sp_rt, D.sp_mk, D.lfsp_list, D.faci, D.lfd, D.lev3idx, D.updp, D.gp_tptr, D.gp_tgt, D.gp_cptr, D.gp_src, D.sw, D.gpart, D.lev2idx, D.lk, D.cl, D.rowidx, D.relidx, D.chidx, D.levidx, D.upd, D.yaa, D.fac, D.tmp, D.tmpptr,
                     D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
-                    D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner};
+                    D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
+                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
@@ -2179,6 +2183,9 @@ int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
       f.resize(S.nsn, 0);
       return put64(f);
     }
+    case CSP_Q_MRC_CLAMPED:
+      if (out) out[0] = c->mrc_clamped;
+      return 1;
   }
   return SMCP_EINVAL;
 }
@@ -3020,6 +3027,168 @@ int csp_trsm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, 
   if (int rc = ready(c)) return rc;
   if (nrhs < 1 || ldb < c->S.n) return SMCP_EINVAL;
   return trsm_impl(c, L, nullptr, B, nrhs, ldb, trans, (hipStream_t)stream);
+}
+
+// ---- minimum-rank completion (front_mrc.hip) ----------------------------------------------------------------------
+constexpr int64_t MRC_LDS = 128 * 1024;     // bytes of dynamic LDS a slot may take (the rest: the reduction buffers, one
+                                            // pair per instantiation of mrc_argmax)
+constexpr int64_t MRC_HBM_DOUBLES = (int64_t)1 << 25;  // HBM slots of one launch: 256 MiB at most (always at least one slot)
+
+static int mrc_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  if (D.mrc_int) return 0;
+  if (int rc = dev_alloc(&D.mrc_int, 2 * c->S.nsn + 4, D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.mrc_xdiag, c->S.n, D.bytes)) return rc;
+  return dev_alloc(&D.mrc_list, c->S.nsn, D.bytes);
+}
+
+extern "C++" {
+// Runs kern over the cliques list[b, e) (host copy; the device copy is D.mrc_list), which ascend in slot size need[]
+// (doubles): those whose slot fits in LDS one workgroup each, in launches by size class, the rest over HBM slots
+template <class K>
+static int mrc_launch(csp_ctx* c, int kid, K kern, MrcArgs a, const std::vector<int64_t>& need, int64_t b, int64_t e,
+                      hipStream_t st) {
+  DeviceCtx& D = c->D;
+  static const bool attr = hipFuncSetAttribute((const void*)k_mrc_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS) == hipSuccess &&
+                           hipFuncSetAttribute((const void*)k_mrc_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS) == hipSuccess;
+  const int64_t lds_max = attr ? MRC_LDS : 65536;
+  int64_t q = b;
+  for (int64_t cap : {(int64_t)8192, (int64_t)16384, (int64_t)32768, (int64_t)65536, MRC_LDS}) {
+    int64_t q2 = q;
+    while (q2 < e && need[q2] * (int64_t)sizeof(double) <= std::min(cap, lds_max)) ++q2;
+    if (q2 > q) {
+      a.lev = D.mrc_list + q;
+      a.cnt = (int)(q2 - q);
+      a.ws = nullptr;
+      launch_lds(c, kid, kern, dim3((unsigned)(q2 - q)), dim3(MRC_NT), (size_t)need[q2 - 1] * sizeof(double), st, a);
+    }
+    q = q2;
+  }
+  if (q < e) {
+    const int64_t slot = (need[e - 1] + 31) / 32 * 32;
+    const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
+    if (G * slot > D.mrc_cap) {
+      if (D.mrc_ws) {
+        HIPCHK(hipStreamSynchronize(st));
+        HIPCHK(hipFree(D.mrc_ws));
+        D.bytes -= D.mrc_cap * (int64_t)sizeof(double);
+        D.mrc_ws = nullptr;
+        D.mrc_cap = 0;
+      }
+      if (int rc = dev_alloc(&D.mrc_ws, G * slot, D.bytes)) return rc;
+      D.mrc_cap = G * slot;
+    }
+    a.lev = D.mrc_list + q;
+    a.cnt = (int)(e - q);
+    a.ws = D.mrc_ws;
+    a.slot = slot;
+    launch(c, kid, kern, dim3((unsigned)G), dim3(MRC_NT), st, a);
+  }
+  return 0;
+}
+}  // extern "C++"
+
+// the cliques of every launch of a pass, each launch's range sorted by slot size, uploaded to D.mrc_list; ranges[l] ..
+// ranges[l + 1] is launch l.  r < 0: pass 1 (one launch over all cliques), else pass 2 (one launch per level, root first)
+static int mrc_lists(csp_ctx* c, int64_t r, std::vector<int64_t>& need, std::vector<int64_t>& ranges, hipStream_t st) {
+  const Symbolic& S = c->S;
+  std::vector<int32_t> list;
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  need.clear();
+  ranges.assign(1, 0);
+  auto add = [&](int64_t b, int64_t e) {
+    tmp.clear();
+    for (int64_t q = b; q < e; ++q) {
+      const int64_t k = S.levidx[q];
+      tmp.push_back({r < 0 ? mrc_slot1(S.nf(k)) : mrc_slot2(S.nn(k), S.na(k), r), (int32_t)k});
+    }
+    std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
+    ranges.push_back((int64_t)list.size());
+  };
+  if (r < 0) add(0, S.nsn);
+  else
+    for (int64_t l = S.nlev - 1; l >= 0; --l) add(S.levptr[l], S.levptr[l + 1]);
+  HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
+  return 0;
+}
+
+static MrcArgs mrc_args(csp_ctx* c, const double* x, double tol) {
+  MrcArgs a{};
+  a.cl = c->D.cl;
+  a.rowidx = c->D.rowidx;
+  a.x = x;
+  a.upd = c->D.upd;
+  a.xdiag = c->D.mrc_xdiag;
+  a.tol = tol;
+  a.rank = c->D.mrc_int;
+  a.flag = c->D.mrc_int + c->S.nsn;
+  return a;
+}
+
+// k_mrc_reduce and the read-back of its three integers
+static int mrc_reduce(csp_ctx* c, hipStream_t st, int32_t* out) {
+  int32_t* dout = c->D.mrc_int + 2 * c->S.nsn;
+  launch(c, KID_mrc_reduce, k_mrc_reduce, dim3(1), dim3(MRC_NT), st, (const int32_t*)c->D.mrc_int,
+         (const int32_t*)(c->D.mrc_int + c->S.nsn), (int)c->S.nsn, dout);
+  HIPCHK(end_call(c));
+  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int csp_mrcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mrc_setup(c)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = mrc_lists(c, -1, need, ranges, st)) return rc;
+  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)c->S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc_xdiag);
+  gather_all(c, x, 0, 1, c->D.upd, st);          // X_AA of every clique
+  if (int rc = mrc_launch(c, KID_mrc_rank, k_mrc_rank, mrc_args(c, x, tol), need, 0, c->S.nsn, st)) return rc;
+  int32_t out[3];
+  if (int rc = mrc_reduce(c, st, out)) return rc;
+  if (out[1]) return out[1];
+  *r = out[0];
+  return 0;
+}
+
+int csp_mrcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !(tol >= 0.0) || r < 0 || r > c->S.max_front || (r > 0 && (!Y || ldY < r)) || c->ntrial != 1) return SMCP_EINVAL;
+  if (r == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mrc_setup(c)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = mrc_lists(c, r, need, ranges, st)) return rc;
+  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)c->S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc_xdiag);
+  MrcArgs a = mrc_args(c, x, tol);
+  a.Y = Y;
+  a.ldY = ldY;
+  a.r = (int)r;
+  for (size_t l = 0; l + 1 < ranges.size(); ++l)
+    if (int rc = mrc_launch(c, KID_mrc_factor, k_mrc_factor, a, need, ranges[l], ranges[l + 1], st)) return rc;
+  HIPCHK(hipMemsetAsync(c->D.mrc_int, 0, c->S.nsn * sizeof(int32_t), st));      // (k_mrc_reduce: ranks unused here)
+  int32_t out[3];
+  if (int rc = mrc_reduce(c, st, out)) return rc;
+  c->mrc_clamped = out[2];
+  return 0;
+}
+
+int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t trials, const double* G, int64_t nedges,
+                    const int64_t* ei, const int64_t* ej, const double* w, int8_t* s, double* cut, void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int64_t n = c->S.n;
+  if (r < 1 || ldY < r || trials < 1 || trials > 65535 || nedges < 0 || !Y || !G || !s || !cut || (nedges && (!ei || !ej || !w)))
+    return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  launch(c, KID_cut_signs, k_cut_signs, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)trials), dim3(MRC_NT), st, n, (int)r,
+         Y, ldY, G, s);
+  launch(c, KID_cut_weights, k_cut_weights, dim3((unsigned)trials), dim3(MRC_NT), st, n, nedges, ei, ej, w, (const int8_t*)s, cut);
+  HIPCHK(end_call(c));
+  return 0;
 }
 
 static int reduce_impl(csp_ctx* c, const double* X, const double* Y, int mode, double* out, hipStream_t st) {

@@ -155,6 +155,10 @@ struct DeviceCtx {
   bool qr_valid = false;       // ustack holds Q and qr_ws the factor for the matrices (qr_L, qr_Y)
   const void* qr_L = nullptr; const void* qr_Y = nullptr;
   int64_t lfd_len = 0;         // doubles of lfd (large-front slots + the dense slot)
+  // minimum-rank completion (front_mrc.hip): per-workgroup HBM slots of the cliques too wide for LDS, per clique rank and
+  // flag (2 nsn) + the reduced results, diag(X), and the cliques of every launch (sorted by slot size within a launch)
+  double* mrc_ws = nullptr; int64_t mrc_cap = 0;
+  int32_t* mrc_int = nullptr; double* mrc_xdiag = nullptr; int32_t* mrc_list = nullptr;
   int64_t bytes = 0;
 };
 
@@ -240,6 +244,7 @@ struct csp_ctx {
   int32_t* xr_roots = nullptr; int32_t* xr_owner = nullptr; int64_t* xr_bptr = nullptr;
   int64_t xr_n = 0; int xr_me = -1; int xr_world = 0; int64_t xr_npmax = 1;
   std::vector<int64_t> xr_size;
+  int64_t mrc_clamped = 0;              // cliques of the last csp_mrcompletion whose Schur factor lost columns to the r-column cap
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy
   // side streams for clique-local launches that do not depend on each other (Fork in capi.hip): created on first use
   hipStream_t aux_stream[2] = {nullptr, nullptr};
