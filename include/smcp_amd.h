@@ -72,9 +72,10 @@ enum {
   CSP_Q_SNODE = 16,
   CSP_Q_FAMILY = 17, /* nsn, after csp_device_init: 2 = small front swept together with its childless children in one
                         workgroup (family kernel of the sparse-input Schur sweeps), 1 = such a child, 0 = neither */
-  CSP_Q_MRC_CLAMPED = 18  /* 1 value: cliques of the last csp_mrcompletion on this context whose Schur-complement factor had
+  CSP_Q_MRC_CLAMPED = 18, /* 1 value: cliques of the last csp_mrcompletion on this context whose Schur-complement factor had
                              more pivots above the threshold than the r columns left room for (0 when r came from
                              csp_mrcompletion_rank with the same X and tol, up to rounding) */
+  CSP_Q_EDM_CLAMPED = 19  /* 1 value: the same for the last csp_edmcompletion (r from csp_edmcompletion_rank) */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -136,6 +137,22 @@ int csp_mrcompletion(csp_ctx* ctx, const double* blkval, double tol, int64_t r, 
  * different signs, summed in a fixed order. */
 int csp_maxcut_cuts(csp_ctx* ctx, const double* Y, int64_t ldY, int64_t r, int64_t trials, const double* G, int64_t nedges,
                     const int64_t* ei, const int64_t* ej, const double* w, int8_t* s, double* cut, void* stream);
+/* chompack.edmcompletion(D), pass 1: D holds squared distances on V (zero diagonal).  *r = max over the cliques g of the
+ * numerical affine dimension of D_gg -- the pivots above tol * max diag(G) of a diagonally pivoted Cholesky of the
+ * centred Gram matrix G = -1/2 (D_gg - rho 1^T - 1 rho^T + sigma 1 1^T), centred on the separator points of g (on g itself
+ * at a root).  Returns 1 + k when clique k has a remaining pivot below -tol * max diag(G): D_gg is not a Euclidean
+ * distance matrix, so D has no Euclidean completion; SMCP_EINVAL for a nonzero diagonal entry.  Synchronises the stream. */
+int csp_edmcompletion_rank(csp_ctx* ctx, const double* blkval, double tol, int64_t* r, void* stream);
+/* chompack.edmcompletion(D), pass 2: points Y (n x r, row i at Y + i*ldY, rows in the permuted order) with
+ * |Y_i - Y_j|^2 = D_ij on V, for the r of csp_edmcompletion_rank (same D and tol); Y is determined up to a rigid motion.
+ * Top-down over the clique tree, per clique the step of csp_mrcompletion on G, centred on the centroid of the separator
+ * rows.  Columns dropped at the r cap: csp_symbolic_query(CSP_Q_EDM_CLAMPED).  Deterministic; synchronises. */
+int csp_edmcompletion(csp_ctx* ctx, const double* blkval, double tol, int64_t r, double* Y, int64_t ldY, void* stream);
+/* chompack.edmcompletion's return form, the dense completed EDM (device arrays): D[i*ldD + j] = |Y_p(i) - Y_p(j)|^2 for
+ * i, j < n, p = perm (n int64 row indices of Y; NULL: the identity), summed over the r columns in a fixed order: exactly
+ * symmetric with a zero diagonal.  perm = the inverse permutation of the symbolic order gives the original order. */
+int csp_edm_dense(csp_ctx* ctx, const double* Y, int64_t ldY, int64_t r, const int64_t* perm, double* D, int64_t ldD,
+                  void* stream);
 /* chompack.dot(X, Y) = tr(XY) on V (solvers.py:399,836,...); result written to *out (host). */
 int csp_dot(csp_ctx* ctx, const double* X, const double* Y, double* out, void* stream);
 /* sum(log(X.diag())) (solvers.py:395,925,934); *out host. */

@@ -468,6 +468,43 @@ def _mrcompletion(X, tol):
     return chordal.mrcompletion(L, tol), L.symb
 
 
+def edmcompletion(D, tol=1e-12, dense=False):
+    """Euclidean distance matrix completion of the sparse symmetric D of squared distances (scipy sparse, either triangle
+    or both; the diagonal absent or zero) on a chordal pattern (chompack.edmcompletion): points Y (numpy, n x r, ORIGINAL
+    order) with |Y_i - Y_j|^2 = D_ij on the pattern of D, r = the largest numerical affine dimension of a clique
+    (smcp_amd.chordal.edmcompletion for the rank and tolerance semantics), or with dense=True the completed n x n EDM.
+    Every stored off-diagonal entry is a distance, explicit zeros included.  ValueError, before any device work, for a
+    nonzero diagonal entry or a pattern that is not chordal (a fill entry would be read as distance 0); ArithmeticError if
+    a clique block is not a Euclidean distance matrix."""
+    import torch
+    from . import chordal
+    from .cspmatrix import cspmatrix
+    from .symbolic import Symbolic, maxcardsearch
+    D = sp.csc_matrix(D)
+    n = D.shape[0]
+    if D.diagonal().any():
+        raise ValueError("edmcompletion: D has a nonzero diagonal entry")
+    C = D.tocoo()
+    low = C.row > C.col
+    if low.any():
+        I, J, V = C.row[low], C.col[low], C.data[low]
+    else:                                   # upper triangle given
+        up = C.row < C.col
+        I, J, V = C.col[up], C.row[up], C.data[up]
+    pat = sp.csc_matrix((np.ones(len(I)), (I, J)), shape=(n, n)) + sp.identity(n, format="csc")
+    symb = Symbolic(pat, maxcardsearch(pat))
+    if symb.fill > 0:
+        raise ValueError("edmcompletion: the pattern of D is not chordal (%d fill entries)" % symb.fill)
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    Dc = cspmatrix.from_entries(symb, I, J, V, device=dev)
+    Y = chordal.edmcompletion(Dc, tol)
+    ip = np.asarray(symb.ip)
+    if dense:
+        perm = torch.from_numpy(ip.astype(np.int64)).to(Y.device)
+        return chordal.edm_dense(symb, Y, perm).cpu().numpy()
+    return Y.cpu().numpy()[ip]
+
+
 def maxcut_round(P, X, trials=64, seed=0, tol=1e-8):
     """Goemans-Williamson rounding of a max-cut relaxation (maxcut_SDP: C = -(Diag(W 1) - W) / 4) at its solution X
     (scipy sparse, e.g. sol['x']): Y = mrcompletion(X, tol), `trials` Gaussian directions g_t drawn with numpy's

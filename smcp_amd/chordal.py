@@ -147,6 +147,43 @@ def mrcompletion(X, tol=1e-12):
     return Y
 
 
+def edmcompletion(D, tol=1e-12):
+    """chompack.edmcompletion(D): points Y (n x r, float64 device tensor, rows in the PERMUTED order) with
+    |Y_i - Y_j|^2 = D_ij on V, for D holding squared distances on a chordal pattern with a zero diagonal.  r is the
+    largest numerical affine dimension of a clique: the pivots of a diagonally pivoted Cholesky of the clique's centred
+    Gram matrix G above tol * max diag(G).  Y is determined up to a rigid motion; the same D gives the same Y bit for bit.
+    D is not changed.  ValueError for a nonzero diagonal entry; ArithmeticError (naming the clique) when a clique block
+    is not a Euclidean distance matrix (its G has a pivot below -tol * max diag(G)): D has no Euclidean completion."""
+    symb = D.symb
+    _ensure(symb)
+    L = _lib.lib()
+    r = ctypes.c_int64(0)
+    rc = L.csp_edmcompletion_rank(symb.handle, D.blkval.data_ptr(), float(tol), ctypes.byref(r), _stream())
+    if rc == -1 and bool((D.diag() != 0).any()):
+        raise ValueError("edmcompletion: D has a nonzero diagonal entry")
+    if rc > 0:
+        raise ArithmeticError("edmcompletion: not a Euclidean distance matrix (clique %d)" % (rc - 1))
+    _chk(rc, "edmcompletion")
+    Y = torch.zeros((symb.n, r.value), dtype=torch.float64, device=D.blkval.device)
+    if r.value:
+        _chk(L.csp_edmcompletion(symb.handle, D.blkval.data_ptr(), float(tol), r.value, Y.data_ptr(), r.value, _stream()),
+             "edmcompletion")
+    return Y
+
+
+def edm_dense(symb, Y, perm=None):
+    """The completed EDM as a dense n x n device tensor: D[i, j] = |Y[p_i] - Y[p_j]|^2 (csp_edm_dense) for Y of
+    edmcompletion, p = perm (int64 device tensor of row indices of Y; None: the identity, the permuted order)."""
+    _ensure(symb)
+    n, r = Y.shape
+    Y = Y.contiguous()
+    out = torch.empty((n, n), dtype=torch.float64, device=Y.device)
+    pp = 0 if perm is None else perm.data_ptr()
+    _chk(_lib.lib().csp_edm_dense(symb.handle, Y.data_ptr() if r else 0, max(r, 1), r, pp, out.data_ptr(), n, _stream()),
+         "edm_dense")
+    return out
+
+
 _ADJ = {False: 0, True: 1, None: 2}
 
 

@@ -30,6 +30,7 @@
 #include "front_famt.hip"
 #include "front_flow.hip"
 #include "front_mrc.hip"
+#include "front_edm.hip"
 
 using namespace smcp;
 
@@ -61,6 +62,7 @@ enum {
   KID_lf_uinv1, KID_lf_uinv2, KID_lf_completion, KID_hess_up_n16, KID_llt_mfma, KID_llt_mfma_hbm, KID_lf_llt,
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
+  KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -79,7 +81,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_lf_dinv1", "k_lf_dinv2", "k_lf_uinv1", "k_lf_uinv2", "k_lf_completion", "k_hess_up_n16",
   "k_llt_mfma<true>", "k_llt_mfma<false>", "k_lf_llt", "k_hess_up_fam",
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
-  "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights"};
+  "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
+  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2186,6 +2189,9 @@ int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
     case CSP_Q_MRC_CLAMPED:
       if (out) out[0] = c->mrc_clamped;
       return 1;
+    case CSP_Q_EDM_CLAMPED:
+      if (out) out[0] = c->edm_clamped;
+      return 1;
   }
   return SMCP_EINVAL;
 }
@@ -3187,6 +3193,109 @@ int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t
   launch(c, KID_cut_signs, k_cut_signs, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)trials), dim3(MRC_NT), st, n, (int)r,
          Y, ldY, G, s);
   launch(c, KID_cut_weights, k_cut_weights, dim3((unsigned)trials), dim3(MRC_NT), st, n, nedges, ei, ej, w, (const int8_t*)s, cut);
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- Euclidean distance matrix completion (front_edm.hip) -----------------------------------------------------------
+// The launches, slots and per-clique buffers are those of the minimum-rank completion (mrc_launch, D.mrc_*); only the
+// pass-2 slot is larger (edm_slot2), so the clique lists are built here.
+
+// edm_lists: mrc_lists with the slot sizes of front_edm.hip
+static int edm_lists(csp_ctx* c, int64_t r, std::vector<int64_t>& need, std::vector<int64_t>& ranges, hipStream_t st) {
+  const Symbolic& S = c->S;
+  std::vector<int32_t> list;
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  need.clear();
+  ranges.assign(1, 0);
+  auto add = [&](int64_t b, int64_t e) {
+    tmp.clear();
+    for (int64_t q = b; q < e; ++q) {
+      const int64_t k = S.levidx[q];
+      tmp.push_back({r < 0 ? mrc_slot1(S.nf(k)) : edm_slot2(S.nn(k), S.na(k), r), (int32_t)k});
+    }
+    std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
+    ranges.push_back((int64_t)list.size());
+  };
+  if (r < 0) add(0, S.nsn);
+  else
+    for (int64_t l = S.nlev - 1; l >= 0; --l) add(S.levptr[l], S.levptr[l + 1]);
+  HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
+  return 0;
+}
+
+// the LDS limit mrc_launch assumes for its own kernels, granted to the two of this file as well
+static void edm_lds_attr() {
+  static const bool once = (hipFuncSetAttribute((const void*)k_edm_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS),
+                            hipFuncSetAttribute((const void*)k_edm_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS),
+                            true);
+  (void)once;
+}
+
+// k_edm_reduce and the read-back of its three integers
+static int edm_reduce(csp_ctx* c, hipStream_t st, int32_t* out) {
+  int32_t* dout = c->D.mrc_int + 2 * c->S.nsn;
+  launch(c, KID_edm_reduce, k_edm_reduce, dim3(1), dim3(MRC_NT), st, (const int32_t*)c->D.mrc_int,
+         (const int32_t*)(c->D.mrc_int + c->S.nsn), (int)c->S.nsn, dout);
+  HIPCHK(end_call(c));
+  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+int csp_edmcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mrc_setup(c)) return rc;
+  edm_lds_attr();
+  std::vector<int64_t> need, ranges;
+  if (int rc = edm_lists(c, -1, need, ranges, st)) return rc;
+  gather_all(c, x, 0, 1, c->D.upd, st);          // D_AA of every clique
+  if (int rc = mrc_launch(c, KID_edm_rank, k_edm_rank, mrc_args(c, x, tol), need, 0, c->S.nsn, st)) return rc;
+  int32_t out[3];
+  if (int rc = edm_reduce(c, st, out)) return rc;
+  if (out[2]) return SMCP_EINVAL;                 // a nonzero diagonal entry
+  if (out[1]) return out[1];
+  *r = out[0];
+  return 0;
+}
+
+int csp_edmcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !(tol >= 0.0) || r < 0 || r > c->S.max_front || (r > 0 && (!Y || ldY < r)) || c->ntrial != 1) return SMCP_EINVAL;
+  c->edm_clamped = 0;
+  if (r == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mrc_setup(c)) return rc;
+  edm_lds_attr();
+  std::vector<int64_t> need, ranges;
+  if (int rc = edm_lists(c, r, need, ranges, st)) return rc;
+  MrcArgs a = mrc_args(c, x, tol);
+  a.Y = Y;
+  a.ldY = ldY;
+  a.r = (int)r;
+  for (size_t l = 0; l + 1 < ranges.size(); ++l)
+    if (int rc = mrc_launch(c, KID_edm_factor, k_edm_factor, a, need, ranges[l], ranges[l + 1], st)) return rc;
+  HIPCHK(hipMemsetAsync(c->D.mrc_int, 0, c->S.nsn * sizeof(int32_t), st));      // (k_mrc_reduce: ranks unused here)
+  int32_t out[3];
+  if (int rc = mrc_reduce(c, st, out)) return rc;
+  c->edm_clamped = out[2];
+  return 0;
+}
+
+int csp_edm_dense(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, const int64_t* perm, double* D, int64_t ldD,
+                  void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int64_t n = c->S.n;
+  if (r < 0 || r > INT32_MAX || (r > 0 && (!Y || ldY < r)) || !D || ldD < n) return SMCP_EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nt = (unsigned)((n + EDM_TILE - 1) / EDM_TILE);
+  if (nt > 65535) return SMCP_EINVAL;
+  launch(c, KID_edm_dense, k_edm_dense, dim3(nt, nt), dim3(MRC_NT), st, n, (int)r, Y, ldY, perm, D, ldD);
   HIPCHK(end_call(c));
   return 0;
 }

@@ -245,6 +245,7 @@ struct csp_ctx {
   int64_t xr_n = 0; int xr_me = -1; int xr_world = 0; int64_t xr_npmax = 1;
   std::vector<int64_t> xr_size;
   int64_t mrc_clamped = 0;              // cliques of the last csp_mrcompletion whose Schur factor lost columns to the r-column cap
+  int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy
   // side streams for clique-local launches that do not depend on each other (Fork in capi.hip): created on first use
   hipStream_t aux_stream[2] = {nullptr, nullptr};
