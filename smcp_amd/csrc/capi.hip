@@ -23,6 +23,7 @@
 #include "front_large.hip"
 #include "front_inv.hip"
 #include "front_n16.hip"
+#include "front_downfam.hip"
 #include "front_fam.hip"
 #include "front_fam2.hip"
 #include "front_lfsp.hip"
@@ -62,7 +63,7 @@ enum {
   KID_lf_uinv1, KID_lf_uinv2, KID_lf_completion, KID_hess_up_n16, KID_llt_mfma, KID_llt_mfma_hbm, KID_lf_llt,
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
-  KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense,
+  KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -82,7 +83,7 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_llt_mfma<true>", "k_llt_mfma<false>", "k_lf_llt", "k_hess_up_fam",
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
-  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense"};
+  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -1639,11 +1640,60 @@ void gather_set(csp_ctx* c, int set, const double* x, int64_t ldx, int nrhs, dou
     launch(c, KID_gather_level, k_gather_level, dim3(cnt, nrhs, gather_parts(std::max(L.namaxI, L.namaxII), (int64_t)cnt * nrhs, c->D.ncu)), dim3(NT), st, a, x, ldx, updbase);
   }
 }
+// family down-sweep (front_downfam.hip) for the nS family parents at the tail of a level's LDS class.  SMCP_DOWN_FAM: the most
+// right-hand sides it serves (0: never, the per-level k_hess_down_w launches)
+int down_fam_maxrhs() {
+  static int v = -1;
+  if (v < 0) v = std::min(65535, std::max(0, sw_int("SMCP_DOWN_FAM", 1)));
+  return v;
+}
+// a: the family parents (list a.t.lev, cnt of them, sizing a.fam*); lone / nlone: childless cliques of the level below outside the
+// families with nn <= 16, na <= 64 (sizing lnn, lna), swept by workgroups of their own in the same launch
+void launch_down_fam(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, int64_t ldu, hipStream_t st,
+                     const int32_t* lone = nullptr, int nlone = 0, int lnn = 0, int lna = 0) {
+  const int nfmax = std::max(a.famnn + a.famna, lnn + lna), cpan = (a.famcnn + a.famcna) * a.famcnn;
+  const size_t bytes = down_fam_lds_bytes(nfmax, cpan);
+  const int pnat = (std::max(std::max(a.famna, lna), 1) + 15) / 16, cnat = (std::max(a.famcna, 1) + 15) / 16;
+  const dim3 grid(cnt + nlone, nrhs), blk(256);
+  switch (2 * pnat + cnat) {
+    case 3: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<1, 1>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 4: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<1, 2>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 5: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<2, 1>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 6: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<2, 2>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 7: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<3, 1>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 8: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<3, 2>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    case 9: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<4, 1>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+    default: launch_lds(c, KID_hess_down_fam, k_hess_down_fam<4, 2>, grid, blk, bytes, st, a, U, ldu, nfmax, cpan, cnt, lone); break;
+  }
+}
 void hess_down_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ysc, int ymode, hipStream_t st, int set = 0,
                     const double* yroot = nullptr) {
   MfmaArgs a0 = mfma_args(c, ysc, ymode, nrhs);
+  MfmaArgs fam1 = a0;      // the family parents of level 1, launched at level 0
+  int nfam1 = 0;
   for (int64_t l = c->S.nlev - 1; l >= 0; --l)
     for_level_classes(c, l, a0, [&](bool lds, MfmaArgs a, int cnt, size_t bytes, int thr) {
+      // families (the tail of the LDS class, as in hess_up_fast): parent and children in one workgroup, the children take their
+      // Z_AA from the parent's front in LDS (front_downfam.hip); the childless members at level 0 are skipped here.  Every
+      // condition is one of the whole sweep, so the two levels of a family decide alike.  The families of level 1 are launched
+      // when the sweep reaches level 0 (everything above is done by then, also the large fronts of level 1), together with the
+      // level-0 cliques outside the families when those fit the kernel: one launch instead of two.
+      if (lds && a.nS > 0 && ymode == 0 && nrhs <= down_fam_maxrhs()) {
+        const int nS = a.nS;
+        a.nS = 0;
+        MfmaArgs af = a;
+        af.t.lev = a.t.lev + (cnt - nS);
+        cnt -= nS;
+        if (a.level > 1) launch_down_fam(c, af, nS, nrhs, U, ldu, st);
+        else if (a.level == 1) { fam1 = af; nfam1 = nS; }
+        else if (nfam1 > 0) {
+          const bool fits = cnt > 0 && a.nnmax <= 16 && a.namax <= 64;
+          launch_down_fam(c, fam1, nfam1, nrhs, U, ldu, st, fits ? a.t.lev : nullptr, fits ? cnt : 0, fits ? a.nnmax : 0, fits ? a.namax : 0);
+          nfam1 = 0;
+          if (fits) return;
+        }
+        if (cnt == 0) return;
+      }
       int g = rhs_groups(cnt, nrhs, lds ? 2048 : 1024);
       if (lds) {
         // (fewer threads per workgroup do NOT help this kernel on the leaves: 0.302 ms per step with 256, 0.330 with 128)
@@ -1682,6 +1732,7 @@ void hess_down_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* 
       }
       else launch_lds(c, KID_hess_down_mfma_hbm, k_hess_down_mfma<false>, dim3(cnt, nrhs), dim3(thr), 0, st, a, U, ldu);
     }, set);
+  if (nfam1 > 0) launch_down_fam(c, fam1, nfam1, nrhs, U, ldu, st);     // (families whose children's level did not come by: cannot happen)
 }
 
 // inverse of the triangular factors in fac (large fronts: blocked over the chip; the rest: one workgroup each)

@@ -32,6 +32,7 @@ static const Switch SWITCHES[] = {
   {"SMCP_N16", "1", "0: no shape-specialised k_hess_up_n16"},
   {"SMCP_OLDLDS", "0", "1: k_hess_up_mfma<true> instead of the padded / n16 kernels"},
   {"SMCP_DOWN_W", "1", "0: k_hess_down_mfma instead of the one-wave k_hess_down_w"},
+  {"SMCP_DOWN_FAM", "1", "most right-hand sides of a root -> leaves sweep that take the one-launch family kernel k_hess_down_fam (0: never; the per-level k_hess_down_w launches)"},
   {"SMCP_FAM", "1", "0: no family kernels (per-level sweeps with the update exchange through HBM)"},
   {"SMCP_FAM2", "1", "0: no sparse-input family kernels (k_fam_sparse, k_fam_terms): k_hess_up_fam"},
   {"SMCP_FAMT", "1", "0: no entry-driven family sweep k_fam_terms (k_fam_sparse instead)"},
