@@ -25,6 +25,7 @@
 #include "front_n16.hip"
 #include "front_downfam.hip"
 #include "front_fam.hip"
+#include "front_upfam.hip"
 #include "front_fam2.hip"
 #include "front_lfsp.hip"
 #include "front_leafgram.hip"
@@ -63,7 +64,7 @@ enum {
   KID_lf_uinv1, KID_lf_uinv2, KID_lf_completion, KID_hess_up_n16, KID_llt_mfma, KID_llt_mfma_hbm, KID_lf_llt,
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
-  KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam,
+  KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -83,7 +84,7 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_llt_mfma<true>", "k_llt_mfma<false>", "k_lf_llt", "k_hess_up_fam",
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
-  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam"};
+  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -1437,6 +1438,49 @@ bool lfsp_dynamic_ok(csp_ctx* c, const MfmaArgs& a) {
   return on && a.kc_ptr && a.ymode == 2 && a.ysc && D.kc_maxlist_large > 0 && D.kc_maxlist_large <= LFSP_ECAP && D.lfsp_cnt;
 }
 
+// family up-sweep for few dense right-hand sides (front_upfam.hip) for the nS family parents at the tail of a level's LDS class.
+// SMCP_UP_FAM: the most right-hand sides it serves (0: never, k_hess_up_fam and the per-level launch of the level-0 outsiders)
+int up_fam_maxrhs() {
+  static int v = -1;
+  if (v < 0) v = std::min(65535, std::max(0, sw_int("SMCP_UP_FAM", 1)));
+  return v;
+}
+// a: the family parents (list a.t.lev, cnt of them, sizing a.fam*); lone / nlone: childless cliques of the level below outside the
+// families with nn <= 16, na <= 64 (sizing lnn, lna), swept by workgroups of their own in the same launch.  false = not
+// launchable (LDS budget, attribute, a size class without a template case): nothing was launched, the caller takes the previous route
+template <int PNAT, int CNAT>
+bool launch_up_fam1_t(csp_ctx* c, const MfmaArgs& a, dim3 grid, size_t bytes, double* U, int64_t ldu, hipStream_t st, int nfmax, int cpan, int cnt, const int32_t* lone) {
+  static bool attr = false;       // (beyond 64 KB: the largest families, two workgroups per CU)
+  if (bytes > 64 * 1024 && !attr) {
+    if (hipFuncSetAttribute((const void*)k_hess_up_fam1<PNAT, CNAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) != hipSuccess) return false;
+    attr = true;
+  }
+  if (a.ysc == c->D.fac) complete_fac(c, st);      // the children's panels are scaled by their own factors
+  launch_lds(c, KID_hess_up_fam1, k_hess_up_fam1<PNAT, CNAT>, grid, dim3(256), bytes, st, a, U, ldu, nfmax, cpan, cnt, lone);
+  return true;
+}
+bool launch_up_fam1(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, int64_t ldu, hipStream_t st,
+                    const int32_t* lone = nullptr, int nlone = 0, int lnn = 0, int lna = 0) {
+  // (a family parent has at most eight children: classify_levels admits no other; the kernel raises the failure flag on a ninth)
+  if (a.famnn > 16 || a.famna > 64 || a.famcnn > 16 || a.famcna > 32 || lnn > 16 || lna > 64 || nrhs > 65535) return false;
+  const int nfmax = std::max(a.famnn + a.famna, lnn + lna), cpan = (a.famcnn + a.famcna) * a.famcnn;
+  const size_t bytes = down_fam_lds_bytes(nfmax, cpan);
+  if (bytes > LDS_LIMIT) return false;
+  const int pnat = (std::max(std::max(a.famna, lna), 1) + 15) / 16, cnat = (std::max(a.famcna, 1) + 15) / 16;
+  const dim3 grid(cnt + nlone, nrhs);
+  switch (2 * pnat + cnat) {
+    case 3: return launch_up_fam1_t<1, 1>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 4: return launch_up_fam1_t<1, 2>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 5: return launch_up_fam1_t<2, 1>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 6: return launch_up_fam1_t<2, 2>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 7: return launch_up_fam1_t<3, 1>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 8: return launch_up_fam1_t<3, 2>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 9: return launch_up_fam1_t<4, 1>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+    case 10: return launch_up_fam1_t<4, 2>(c, a, grid, bytes, U, ldu, st, nfmax, cpan, cnt, lone);
+  }
+  return false;
+}
+
 // sparse_j0 >= 0: the right-hand sides are the constraints sparse_j0 .. (through `ids` if given) and are taken from
 // their per-clique entry lists (MfmaArgs::kc_*) -- U is output only and need not be cleared or scattered into
 // yroot: the projected inverse Y (blkval) when the caller runs the down sweep right after this one (hessian(adj = None)):
@@ -1505,14 +1549,34 @@ void hess_up_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ys
   auto dense_input = [&](MfmaArgs& a, int cnt) { dense_input_on(a, cnt, U, nrhs, st); };
   // (A handful of level-0 fronts outside the families -- synth50k: ONE leaf hangs off a mid front directly -- is a launch of
   // its own in the chain, 15 us for one workgroup.  On a side stream next to the family launch of level 1 it costs as
-  // much in event waits: 6 us before and after the family launch, measured.)
-  for (int64_t l = lev_lo; l < (lev_hi < 0 ? c->S.nlev : lev_hi); ++l) {    // [lev_lo, lev_hi): the caller may sweep in two parts
+  // much in event waits: 6 us before and after the family launch, measured.  For few dense right-hand sides they ride along in
+  // the family launch of level 1, k_hess_up_fam1: the level-0 pass hands them over in `out0`.)
+  const int64_t lev_end = lev_hi < 0 ? c->S.nlev : lev_hi;
+  const bool up1 = !sparse && nrhs <= up_fam_maxrhs();     // dense input, few right-hand sides: the resident family kernel
+  struct { MfmaArgs a; int cnt = 0; size_t bytes = 0; int thr = 0; } out0;      // level-0 outsiders waiting for that launch
+  // a list of small fronts by the per-level kernels
+  auto small_level = [&](MfmaArgs& a, int cnt, size_t bytes, int thr) {
+    const int g = rhs_groups(cnt, nrhs, 2048);
+    hipStream_t ls = st;
+    static int oldk = -1;
+    if (oldk < 0) { const char* e = sw_str("SMCP_OLDLDS"); oldk = (e && e[0] == '1') ? 1 : 0; }
+    size_t pbytes = (size_t)pad_layout(a.nnmax, a.namax, a.nchmax, a.panmax, a.pkmax, a.plansum).total * sizeof(double);
+    if (!oldk && try_n16(c, a, cnt, nrhs, U, ldu, ls)) {
+    } else if (!oldk && pbytes <= LDS_LIMIT) {
+      dense_input_on(a, cnt, U, nrhs, ls);
+      launch_lds(c, KID_hess_up_pad, k_hess_up_pad, dim3(cnt, g), dim3(pbytes > 48 * 1024 ? 512 : 256), pbytes, ls, a, U, ldu);
+    } else {
+      dense_input_on(a, cnt, U, nrhs, ls);
+      launch_lds(c, KID_hess_up_mfma, k_hess_up_mfma<true>, dim3(cnt, g), dim3(thr), bytes, ls, a, U, ldu);
+    }
+  };
+  for (int64_t l = lev_lo; l < lev_end; ++l) {    // [lev_lo, lev_hi): the caller may sweep in two parts
     for_level_classes(c, l, a0, [&](bool lds, MfmaArgs a, int cnt, size_t bytes, int thr) {
       static int fam_minrhs = -1;
       if (fam_minrhs < 0) { const char* e = sw_str("SMCP_FAM_MINRHS"); fam_minrhs = e ? atoi(e) : 1; }
       if (lds && a.nS > 0 && (sparse || nrhs >= fam_minrhs)) {
-        // families: the childless members (level 0) are swept inside their parents' workgroups (k_hess_up_fam);
-        // for one or two dense right-hand sides the per-workgroup set-up outweighs the saved exchange (measured)
+        // families: the childless members (level 0) are swept inside their parents' workgroups (k_hess_up_fam, k_hess_up_fam1);
+        // for one or two dense right-hand sides the per-workgroup set-up of k_hess_up_fam outweighs the saved exchange (measured)
         const int nS = a.nS;
         a.nS = 0;
         if (a.level > 0) {
@@ -1521,6 +1585,14 @@ void hess_up_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ys
           if (fgroups_on && (size_t)l < c->famt_grp.size() && c->famt_grp[(size_t)l].ngroups > 0) {
             af.grp_ptr = c->famt_grp[(size_t)l].ptr; af.grp_list = c->famt_grp[(size_t)l].list; af.famt_ngrp = c->famt_grp[(size_t)l].ngroups;
           }
+          // The family launch is the first of its level: a front of this level outside the families may be the parent of a
+          // level-0 outsider and reads its update.  Not launchable: the outsiders take their own launch, here, then k_hess_up_fam.
+          const bool took1 = up1 && !af.famt_ngrp &&
+                             launch_up_fam1(c, af, nS, nrhs, U, ldu, st, out0.cnt ? out0.a.t.lev : nullptr, out0.cnt, out0.cnt ? out0.a.nnmax : 0, out0.cnt ? out0.a.namax : 0);
+          if (!took1 && out0.cnt) small_level(out0.a, out0.cnt, out0.bytes, out0.thr);
+          out0.cnt = 0;
+          if (took1) {
+          } else
           if (!try_fam(c, af, nS, nrhs, U, ldu, st)) {
             // the level-0 members were skipped for this kernel: without it their panels and the parents' updates
             // would be missing, so the call must fail (end_call returns SMCP_EHIP)
@@ -1530,22 +1602,18 @@ void hess_up_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ys
         }
         cnt -= nS;
         if (cnt == 0) return;
-      }
-      int g = rhs_groups(cnt, nrhs, lds ? 2048 : 1024);
-      if (lds) {
-        hipStream_t ls = st;
-        static int oldk = -1;
-        if (oldk < 0) { const char* e = sw_str("SMCP_OLDLDS"); oldk = (e && e[0] == '1') ? 1 : 0; }
-        size_t pbytes = (size_t)pad_layout(a.nnmax, a.namax, a.nchmax, a.panmax, a.pkmax, a.plansum).total * sizeof(double);
-        if (!oldk && try_n16(c, a, cnt, nrhs, U, ldu, ls)) {
-        } else if (!oldk && pbytes <= LDS_LIMIT) {
-          dense_input_on(a, cnt, U, nrhs, ls);
-          launch_lds(c, KID_hess_up_pad, k_hess_up_pad, dim3(cnt, g), dim3(pbytes > 48 * 1024 ? 512 : 256), pbytes, ls, a, U, ldu);
-        } else {
-          dense_input_on(a, cnt, U, nrhs, ls);
-          launch_lds(c, KID_hess_up_mfma, k_hess_up_mfma<true>, dim3(cnt, g), dim3(thr), bytes, ls, a, U, ldu);
+        // level-0 cliques outside the families: into the family launch of level 1 when that level is part of this call, holds
+        // families (they are swept first there: for_level_classes visits the LDS class first, and the family conditions above
+        // are those of the whole sweep, alike at both levels) and the cliques fit the kernel's size class.  The decision is one
+        // per class, on the maxima over ALL small cliques of level 0 (family children included): one outsider with na > 64
+        // keeps every outsider of the level on the per-level launch
+        if (up1 && a.level == 0 && l + 1 < lev_end && a.nnmax <= 16 && a.namax <= 64) {
+          const LevelClass& L1 = set ? c->sets[set].lvl[l + 1] : c->lvl[l + 1];
+          if (L1.nI > 0 && L1.nS > 0) { out0.a = a; out0.cnt = cnt; out0.bytes = bytes; out0.thr = thr; return; }
         }
-      } else if (use_large() && c->D.gp_tptr) {
+      }
+      if (lds) small_level(a, cnt, bytes, thr);
+      else if (use_large() && c->D.gp_tptr) {
         {
           const csp_ctx::LfspGroups* grp = groups_on && (size_t)l < c->lfsp_grp.size() && c->lfsp_grp[(size_t)l].ngroups > 0 ? &c->lfsp_grp[(size_t)l] : nullptr;
           if (sparse && try_lfsp(c, a, cnt, nrhs, U, ldu, st, grp)) return;
@@ -1626,6 +1694,10 @@ void hess_up_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ys
       }
       else { dense_input(a, cnt); launch_lds(c, KID_hess_up_mfma_hbm, k_hess_up_mfma<false>, dim3(cnt, nrhs), dim3(thr), 0, st, a, U, ldu); }
     }, set);
+  }
+  if (out0.cnt) {      // outsiders whose family launch did not come by (cannot happen): sweeping them now would be behind their parents
+    fprintf(stderr, "smcp_amd: level-0 cliques handed to a family launch that was never issued\n");
+    if (!c->launch_err) c->launch_err = -1;
   }
 }
 // the same for the cliques of a set of the partition (1 = owned, 2 = replicated top), root -> leaves
