@@ -7,6 +7,9 @@
  * call it replaces.  Conventions (observed at the reference's call sites):
  *   - operations are IN PLACE on a flat fp64 vector `blkval` (clique k owns a dense
  *     column-major (nn+na) x nn block at blkptr[k]); the caller owns all numeric buffers;
+ *   - the strict upper triangle of every X_NN block (the blkval slots that belong to no entry of V) is zero on entry
+ *     and left zero on exit of every operation; the leading dimensions ldu, ldb and ldh may exceed the packed size
+ *     (blklen, n, m), and the padding between the columns is never written;
  *   - all numeric pointers are DEVICE pointers (HBM) unless a parameter says "host";
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - return value: 0 ok; k>0 = clique k-1 (or pivot) was not positive definite, which the

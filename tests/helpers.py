@@ -23,6 +23,48 @@ PATTERNS = {
 }
 
 
+# the patterns of the GPU suite: the six small ones plus the shapes that select the device's other kernel classes
+GPU_PATTERNS = dict(PATTERNS)
+GPU_PATTERNS["arrow_big"] = lambda: problems.block_arrow_pattern(12, 64, 128)
+GPU_PATTERNS["nested_mid"] = lambda: problems.nested_block_arrow_pattern(nsub=2, nmid=6, nleaf_per_mid=8, seed=3)
+GPU_PATTERNS["dense200"] = lambda: problems.band_pattern(200, 199)
+GPU_PATTERNS["arrow_thin"] = lambda: problems.block_arrow_pattern(6, 2, 150)   # thin cliques, separators beyond LDS
+GPU_PATTERNS["diag"] = lambda: problems.band_pattern(15, 0)          # LP case: every clique is 1 x 1
+# single fronts beyond the one-workgroup class (272 rows): the one-launch blocked Cholesky (front_flow.hip) factors the root
+# (dense600; arrow_one's 310 x 310 root) and the 300 x 300 Y_AA block of arrow_one's only top front
+GPU_PATTERNS["dense600"] = lambda: problems.band_pattern(600, 599)
+GPU_PATTERNS["arrow_one"] = lambda: problems.nested_block_arrow_pattern(nsub=1, nmid=2, nleaf_per_mid=2, leaf=(3, 9), mid=(6, 20), top=(40, 300),
+                                                                        root=310, seed=9)
+# three top fronts in ONE level whose separators (300, 200 and 150 rows of a 310-column root) are beyond the one-workgroup class:
+# their chol(Y_AA) runs side by side in one launch of the one-launch blocked Cholesky (front_flow.hip, gridDim.y = 3; orders 5 / 4 / 3
+# tiles against a plan laid out for 5)
+def _three_tops_pattern():
+    root = np.arange(130, 440)
+    cl = [(root, root)]
+    for s_, na in enumerate((300, 200, 150)):
+        own = np.arange(40 * s_, 40 * s_ + 40)
+        sep = root[np.sort(np.random.default_rng(90 + s_).choice(len(root), size=na, replace=False))]
+        cl.append((own, np.concatenate([own, sep])))
+    cl.append((np.arange(120, 130), np.concatenate([np.arange(120, 130), root[:20]])))
+    return problems._from_cliques(440, cl)
+
+
+GPU_PATTERNS["three_tops"] = _three_tops_pattern
+# families (front_fam.hip: small parents swept together with their childless children): largest member sizes,
+# odd sizes with few children, and nine children per parent (one more than the waves of a workgroup: no family)
+GPU_PATTERNS["fam_max"] = lambda: problems.nested_block_arrow_pattern(nsub=1, nmid=3, nleaf_per_mid=8, leaf=(16, 32),
+                                                                      mid=(16, 64), top=(40, 50), root=60, seed=5)
+GPU_PATTERNS["fam_odd"] = lambda: problems.nested_block_arrow_pattern(nsub=2, nmid=4, nleaf_per_mid=5, leaf=(3, 17),
+                                                                      mid=(7, 33), top=(20, 30), root=40, seed=6)
+GPU_PATTERNS["fam_nine"] = lambda: problems.nested_block_arrow_pattern(nsub=1, nmid=2, nleaf_per_mid=9, leaf=(2, 9),
+                                                                       mid=(6, 20), top=(20, 20), root=30, seed=7)
+
+
+# odd-sized families under top fronts beyond the LDS class (nf = 130 <= 198): the fused extend-add with three row tiles
+GPU_PATTERNS["fam_top"] = lambda: problems.nested_block_arrow_pattern(nsub=2, nmid=5, nleaf_per_mid=3, leaf=(3, 17),
+                                                                      mid=(7, 33), top=(30, 100), root=110, seed=8)
+
+
 def make(name):
     pat = PATTERNS[name]()
     symb = Symbolic(pat)
