@@ -156,6 +156,15 @@ int csp_edmcompletion(csp_ctx* ctx, const double* blkval, double tol, int64_t r,
  * symmetric with a zero diagonal.  perm = the inverse permutation of the symbolic order gives the original order. */
 int csp_edm_dense(csp_ctx* ctx, const double* Y, int64_t ldY, int64_t r, const int64_t* perm, double* D, int64_t ldD,
                   void* stream);
+/* chompack.psdcompletion(X): the dense maximum-determinant positive semidefinite completion Xd (n x n device array, entry
+ * (i, j) at Xd + i*ldX + j, the permuted order; exactly symmetric, equal to X on V bit for bit).  For X positive definite on
+ * V its inverse vanishes off V.  Top-down over the levels of the clique tree: Xd[E, N] = Xd[E, A] W for the columns N and
+ * separator A of a clique and the rows E completed before, W the basic solution of X_AA W = X_AN from a diagonally pivoted
+ * Cholesky of X_AA (pivots above tol * max diag(X_AA)): no inverse but those of the separator blocks, no Schur complement,
+ * so X may be singular.  Entries between different components of the pattern are zero.  Returns 1 + k when clique k is
+ * not positive semidefinite (the test of csp_mrcompletion_rank), SMCP_EINVAL for ldX < n.  X is not changed.
+ * Deterministic; synchronises the stream. */
+int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd, int64_t ldX, void* stream);
 /* chompack.dot(X, Y) = tr(XY) on V (solvers.py:399,836,...); result written to *out (host). */
 int csp_dot(csp_ctx* ctx, const double* X, const double* Y, double* out, void* stream);
 /* sum(log(X.diag())) (solvers.py:395,925,934); *out host. */

@@ -468,6 +468,18 @@ def _mrcompletion(X, tol):
     return chordal.mrcompletion(L, tol), L.symb
 
 
+def psdcompletion(X, tol=1e-12):
+    """Maximum-determinant positive semidefinite completion of the sparse symmetric X (scipy sparse, either triangle or
+    both), returned as a dense numpy array in the ORIGINAL order (chompack.psdcompletion; smcp_amd.chordal.psdcompletion
+    for the tolerance semantics).  For positive definite X this is the matrix completion() returns; unlike completion()
+    it also takes an X that is singular on some cliques, such as an interior-point solution sol['x'].  The pattern is
+    embedded as in completion().  ArithmeticError if X has no positive semidefinite completion."""
+    from . import chordal
+    L, _ = _on_pattern(X)
+    ip = np.asarray(L.symb.ip)
+    return chordal.psdcompletion(L, tol).cpu().numpy()[np.ix_(ip, ip)]
+
+
 def edmcompletion(D, tol=1e-12, dense=False):
     """Euclidean distance matrix completion of the sparse symmetric D of squared distances (scipy sparse, either triangle
     or both; the diagonal absent or zero) on a chordal pattern (chompack.edmcompletion): points Y (numpy, n x r, ORIGINAL

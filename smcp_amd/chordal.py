@@ -147,6 +147,22 @@ def mrcompletion(X, tol=1e-12):
     return Y
 
 
+def psdcompletion(X, tol=1e-12):
+    """chompack.psdcompletion(X): the maximum-determinant positive semidefinite completion of X as a dense n x n float64
+    device tensor, rows and columns in the PERMUTED order; it equals X on V bit for bit and is exactly symmetric.  For X
+    positive definite on V its inverse vanishes off V (what base.completion returns); X may also be singular: the
+    separator blocks X_AA are solved with a diagonally pivoted Cholesky whose pivots count while above
+    tol * max diag(X_AA), and nothing else is inverted.  Entries between different components of the pattern are zero.
+    X is not changed.  ArithmeticError (naming the clique) when a clique block has a pivot below -tol * max diag(X_gg): X
+    has no positive semidefinite completion."""
+    symb = X.symb
+    _ensure(symb)
+    out = torch.empty((symb.n, symb.n), dtype=torch.float64, device=X.blkval.device)
+    _chk(_lib.lib().csp_psdcompletion(symb.handle, X.blkval.data_ptr(), float(tol), out.data_ptr(), symb.n, _stream()),
+         "psdcompletion")
+    return out
+
+
 def edmcompletion(D, tol=1e-12):
     """chompack.edmcompletion(D): points Y (n x r, float64 device tensor, rows in the PERMUTED order) with
     |Y_i - Y_j|^2 = D_ij on V, for D holding squared distances on a chordal pattern with a zero diagonal.  r is the

@@ -33,6 +33,7 @@
 #include "front_flow.hip"
 #include "front_mrc.hip"
 #include "front_edm.hip"
+#include "front_psd.hip"
 
 using namespace smcp;
 
@@ -65,6 +66,7 @@ enum {
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
   KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
+  KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -84,7 +86,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_llt_mfma<true>", "k_llt_mfma<false>", "k_lf_llt", "k_hess_up_fam",
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
-  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1"};
+  "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
+  "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2257,7 +2260,7 @@ void csp_symbolic_destroy(csp_ctx* c) {
     void* ptrs[] = {D.lfsp_skip, D.famt_skip, D.both_skip, D.trsm_x, D.fp, D.fp_bad, D.gsl_start, D.gsl_len, D.lg_list, D.lg_slot, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.sp_rt, D.sp_mk, D.lfsp_list, D.faci, D.lfd, D.lev3idx, D.updp, D.gp_tptr, D.gp_tgt, D.gp_cptr, D.gp_src, D.sw, D.gpart, D.lev2idx, D.lk, D.cl, D.rowidx, D.relidx, D.chidx, D.levidx, D.upd, D.yaa, D.fac, D.tmp, D.tmpptr,
                     D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
                     D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
-                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list};
+                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
@@ -3419,6 +3422,112 @@ int csp_edm_dense(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, const int
   const unsigned nt = (unsigned)((n + EDM_TILE - 1) / EDM_TILE);
   if (nt > 65535) return SMCP_EINVAL;
   launch(c, KID_edm_dense, k_edm_dense, dim3(nt, nt), dim3(MRC_NT), st, n, (int)r, Y, ldY, perm, D, ldD);
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- dense maximum-determinant PSD completion (front_psd.hip) -------------------------------------------------------
+// ulist (the columns in the order the levels complete them, root level first, cliques ascending inside a level), the tile
+// tasks of the two fill launches of every level and the W workspace: built on the first call
+static int psd_setup(csp_ctx* c, hipStream_t st) {
+  DeviceCtx& D = c->D;
+  if (D.psd_ulist) return 0;
+  const Symbolic& S = c->S;
+  std::vector<int32_t> ulist;
+  std::vector<PsdTask> tasks;
+  std::vector<int64_t> end_of(S.nsn, 0);
+  c->psd_lev.clear();
+  const int64_t max_tasks = (int64_t)1 << 26;
+  for (int64_t l = S.nlev - 1; l >= 0; --l) {
+    std::vector<int64_t> ks(S.levidx.begin() + S.levptr[l], S.levidx.begin() + S.levptr[l + 1]);
+    std::sort(ks.begin(), ks.end());
+    const int64_t before = (int64_t)ulist.size();
+    for (int64_t k : ks) {
+      for (int64_t j = S.snptr[k]; j < S.snptr[k + 1]; ++j) ulist.push_back((int32_t)j);
+      end_of[k] = (int64_t)ulist.size();
+    }
+    const int64_t after = (int64_t)ulist.size();
+    csp_ctx::PsdLevel L;
+    auto add = [&](int64_t k, int64_t b, int64_t e) {
+      for (int64_t off = b; off < e; off += LT)
+        for (int64_t n0 = 0; n0 < S.nn(k); n0 += LT)
+          tasks.push_back({(int32_t)k, (int32_t)off, (int32_t)std::min<int64_t>(LT, e - off), (int32_t)n0});
+    };
+    L.b1 = (int64_t)tasks.size();
+    for (int64_t k : ks) if (S.na(k) > 0) add(k, 0, before);                 // step 1: the rows of the levels done
+    L.b2 = (int64_t)tasks.size();
+    for (int64_t k : ks) if (S.na(k) > 0) add(k, end_of[k], after);          // step 2: the later cliques of the level
+    L.e2 = (int64_t)tasks.size();
+    if (L.e2 > max_tasks) return SMCP_ENOMEM;
+    if (L.e2 > L.b1) c->psd_lev.push_back(L);
+  }
+  if (int rc = dev_alloc(&D.psd_tasks, (int64_t)tasks.size(), D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.psd_w, S.blklen(), D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.psd_idx, S.sepptr[S.nsn], D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.psd_ra, S.nsn, D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.psd_ulist, S.n, D.bytes)) return rc;
+  if (!tasks.empty()) HIPCHK(hipMemcpyAsync(D.psd_tasks, tasks.data(), tasks.size() * sizeof(PsdTask), hipMemcpyHostToDevice, st));
+  if (!ulist.empty()) HIPCHK(hipMemcpyAsync(D.psd_ulist, ulist.data(), ulist.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (host temporaries)
+  return 0;
+}
+
+// the cliques with a separator, ascending in slot size, uploaded to D.mrc_list
+static int psd_lists(csp_ctx* c, std::vector<int64_t>& need, hipStream_t st) {
+  const Symbolic& S = c->S;
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  for (int64_t k = 0; k < S.nsn; ++k)
+    if (S.na(k) > 0) tmp.push_back({psd_slot(S.na(k)), (int32_t)k});
+  std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+  std::vector<int32_t> list;
+  need.clear();
+  for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
+  if (!list.empty()) HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
+  return 0;
+}
+
+int csp_psdcompletion(csp_ctx* c, const double* x, double tol, double* Xd, int64_t ldX, void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int64_t n = c->S.n, nsn = c->S.nsn;
+  if (!x || !Xd || !(tol >= 0.0) || ldX < n || c->ntrial != 1) return SMCP_EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  DeviceCtx& D = c->D;
+  if (int rc = mrc_setup(c)) return rc;
+  if (int rc = psd_setup(c, st)) return rc;
+  static const bool attr = (hipFuncSetAttribute((const void*)k_psd_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS), true);
+  (void)attr;
+  // is every clique block positive semidefinite?  (pass 1 of the minimum-rank completion)
+  std::vector<int64_t> need, ranges;
+  if (int rc = mrc_lists(c, -1, need, ranges, st)) return rc;
+  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)nsn), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, x, D.mrc_xdiag);
+  gather_all(c, x, 0, 1, D.upd, st);          // X_AA of every clique
+  MrcArgs a = mrc_args(c, x, tol);
+  if (int rc = mrc_launch(c, KID_mrc_rank, k_mrc_rank, a, need, 0, nsn, st)) return rc;
+  int32_t out[3];
+  if (int rc = mrc_reduce(c, st, out)) return rc;
+  if (out[1]) return out[1];
+  launch(c, KID_psd_zero, k_psd_zero, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)std::min<int64_t>(n, 1024)), dim3(MRC_NT), st,
+         n, Xd, ldX);
+  launch(c, KID_psd_scatter, k_psd_scatter, dim3((unsigned)nsn), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const int32_t*)D.rowidx, x,
+         Xd, ldX);
+  if (int rc = psd_lists(c, need, st)) return rc;
+  a.pw = D.psd_w;
+  a.pidx = D.psd_idx;
+  a.pra = D.psd_ra;
+  if (int rc = mrc_launch(c, KID_psd_solve, k_psd_solve, a, need, 0, (int64_t)need.size(), st)) return rc;
+  PsdFillArgs f{D.cl, D.rowidx, nullptr, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra, Xd, ldX};
+  for (const csp_ctx::PsdLevel& L : c->psd_lev) {
+    if (L.b2 > L.b1) {
+      f.tasks = D.psd_tasks + L.b1;
+      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.b2 - L.b1)), dim3(256), st, f);
+    }
+    if (L.e2 > L.b2) {
+      f.tasks = D.psd_tasks + L.b2;
+      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.e2 - L.b2)), dim3(256), st, f);
+    }
+  }
   HIPCHK(end_call(c));
   return 0;
 }

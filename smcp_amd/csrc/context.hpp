@@ -25,6 +25,8 @@ struct CliqueDesc {
   int32_t pad;     // slot of this clique among the large (HBM-class) fronts, -1 otherwise
 };
 
+struct PsdTask;
+
 struct DeviceCtx {
   int device = -1;
   int ncu = 256;           // compute units of the device (csp_device_init): launch heuristics
@@ -159,6 +161,10 @@ struct DeviceCtx {
   // flag (2 nsn) + the reduced results, diag(X), and the cliques of every launch (sorted by slot size within a launch)
   double* mrc_ws = nullptr; int64_t mrc_cap = 0;
   int32_t* mrc_int = nullptr; double* mrc_xdiag = nullptr; int32_t* mrc_list = nullptr;
+  // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
+  // W_k[rho] (at its panel offset), the rows A[rho] (at its separator offset) and |rho|
+  struct PsdTask* psd_tasks = nullptr; int32_t* psd_ulist = nullptr;
+  double* psd_w = nullptr; int32_t* psd_idx = nullptr; int32_t* psd_ra = nullptr;
   int64_t bytes = 0;
 };
 
@@ -246,6 +252,8 @@ struct csp_ctx {
   std::vector<int64_t> xr_size;
   int64_t mrc_clamped = 0;              // cliques of the last csp_mrcompletion whose Schur factor lost columns to the r-column cap
   int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
+  struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
+  std::vector<PsdLevel> psd_lev;        // per level with fill work, root first
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy
   // side streams for clique-local launches that do not depend on each other (Fork in capi.hip): created on first use
   hipStream_t aux_stream[2] = {nullptr, nullptr};

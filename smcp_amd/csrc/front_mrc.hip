@@ -43,6 +43,9 @@ struct MrcArgs {
   double* Y;                // pass 2: n x r, row i at Y + i * ldY (permuted order)
   int64_t ldY;
   int r;
+  double* pw;               // k_psd_solve (front_psd.hip): W_k[rho] of every clique, A[rho], |rho|
+  int32_t* pidx;
+  int32_t* pra;
 };
 
 // (value, index) of the largest val(i), i < n; ties go to the lowest index, -1 when every value is -inf / NaN.  The
@@ -82,8 +85,9 @@ __device__ inline int mrc_argmax(int n, F val, double& best) {
 // A's row order (zero in the rows pivoted before), goes to L + j * ldl when L is given.  lv: n doubles, done: n ints of
 // scratch.  Returns the number of pivots; *neg = 1 when the factorisation ran to the threshold and a remaining diagonal
 // entry is below -thr (A is not positive semidefinite), *more = 1 when it stopped at maxcols with a pivot above thr left.
+// piv (optional, n ints): piv[j] = the row pivot j took.
 __device__ inline int mrc_pchol(int n, double* A, int64_t lda, double thr, int maxcols, double* L, int64_t ldl,
-                                double* lv, int* done, int* neg, int* more) {
+                                double* lv, int* done, int* neg, int* more, int* piv = nullptr) {
   for (int i = SMCP_TID; i < n; i += MRC_NT) done[i] = 0;
   __syncthreads();
   *neg = 0;
@@ -101,7 +105,10 @@ __device__ inline int mrc_pchol(int n, double* A, int64_t lda, double thr, int m
       if (L) L[i + j * ldl] = i == p ? s : v;
     }
     __syncthreads();
-    if (SMCP_TID == 0) done[p] = 1;
+    if (SMCP_TID == 0) {
+      done[p] = 1;
+      if (piv) piv[j] = p;
+    }
     for (int e = SMCP_TID; e < n * n; e += MRC_NT) {       // trailing update; pivoted rows have lv = 0
       const int i = e % n, k = e / n;
       if (i >= k) A[i + (int64_t)k * lda] -= lv[i] * lv[k];
