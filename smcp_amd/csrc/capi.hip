@@ -21,6 +21,7 @@
 #include "front_generic.hip"
 #include "front_mfma.hip"
 #include "front_large.hip"
+#include "front_top.hip"
 #include "front_inv.hip"
 #include "front_n16.hip"
 #include "front_downfam.hip"
@@ -66,7 +67,7 @@ enum {
   KID_hess_up_fam, KID_qr_rmul, KID_qr_dots, KID_qr_comb, KID_qr_small, KID_fam2_prep, KID_mid_chol, KID_lf_diag_inv, KID_lfsp_up, KID_lfsp_prep, KID_leaf_gram, KID_leaf_tables, KID_fam_sparse, KID_gram_diag128, KID_lf_assemble_lds, KID_fam_terms, KID_famt_prep, KID_lf_assemble_lds_dyn, KID_lf_zsp, KID_fam_terms_grp, KID_lf_assemble_fz, KID_factor_inverse_lds, KID_chol_flow,
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
   KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
-  KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill,
+  KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill, KID_top_chol, KID_lf_trtri,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -87,7 +88,7 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
   "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
-  "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill"};
+  "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -867,10 +868,24 @@ bool flow_chol(csp_ctx* c, hipStream_t st, double* A, int64_t ld, int n, double*
   return true;
 }
 
-void lf_chol(csp_ctx* c, const MfmaArgs& a, int cnt, double* x, hipStream_t st) {
+// fronts of at most TOP_MAXROWS rows: the register-resident one-workgroup Cholesky k_top_chol (front_top.hip), which can leave
+// Li = L_NN^-1 behind as well; SMCP_TOP_FUSED=0: k_mid_chol, and k_lf_diag_inv / k_lf_trtri for the inverse
+bool use_top(int rowsmax) {
+  static int g = -1;
+  if (g < 0) g = sw_on("SMCP_TOP_FUSED", 1);
+  return g == 1 && rowsmax <= TOP_MAXROWS && use_mid(rowsmax);
+}
+// with_li: the caller wants Li of these fronts in D.lk as well (the scaling point's last level) and skips that part of lf_prep
+// when the route taken supplies it -- use_top(nnmax + namax), the same test as here
+void lf_chol(csp_ctx* c, const MfmaArgs& a, int cnt, double* x, hipStream_t st, bool with_li = false) {
   dim3 blk(256);
   const int nfmax = a.nnmax + a.namax;
   lf_assemble(c, a, cnt, 1, x, 0, 0, st, true);      // (clears the update blocks first where its route does not assign them whole)
+  if (use_top(nfmax)) {
+    if (with_li) launch(c, KID_top_chol, k_top_chol<true>, dim3(cnt), dim3(1024), st, a, x, c->D.lk);
+    else launch(c, KID_top_chol, k_top_chol<false>, dim3(cnt), dim3(1024), st, a, x, (double*)nullptr);
+    return;
+  }
   if (use_mid(nfmax)) {
     launch_lds(c, KID_mid_chol, k_mid_chol, dim3(cnt), dim3(1024), mid_chol_lds(nfmax), st, a, x, (double*)nullptr, 0);
     return;
@@ -909,11 +924,13 @@ void lf_factor_yaa(csp_ctx* c, const MfmaArgs& a, int cnt, double* fac, hipStrea
   }
 }
 // inverse-form factor of the large fronts of one level
-void lf_prep(csp_ctx* c, const MfmaArgs& a, int cnt, const double* L, hipStream_t st) {
+// have_li: Li of these fronts is in D.lk already (k_top_chol<true>); only K = L_AN Li remains
+void lf_prep(csp_ctx* c, const MfmaArgs& a, int cnt, const double* L, hipStream_t st, bool have_li = false) {
   dim3 blk(256);
   static int hoist = -1;
   if (hoist < 0) { const char* e = sw_str("SMCP_MID"); hoist = (e && e[0] == '0') ? 0 : 1; }
-  if (hoist) {
+  if (have_li) {
+  } else if (hoist) {
     // the diagonal blocks' inverses do not depend on each other: one launch for all of them, then the block rows
     launch_lds(c, KID_lf_diag_inv, k_lf_diag_inv, dim3(cnt, tiles64(a.nnmax)), blk, LF_DIAG_LDS, st, a, L, c->D.lk);
     static int rec = -1;
@@ -923,7 +940,7 @@ void lf_prep(csp_ctx* c, const MfmaArgs& a, int cnt, const double* L, hipStream_
       for (int b = LB; b < a.nnmax; b *= 2) {
         const int pairs = (a.nnmax + 2 * b - 1) / (2 * b), tpb = b / LB;
         for (int step = 0; step < 2; ++step)
-          launch(c, KID_lf_prep_s, k_lf_trtri, dim3(umax1(pairs * tpb * tpb), cnt), blk, st, a, L, c->D.lk, b, step);
+          launch(c, KID_lf_trtri, k_lf_trtri, dim3(umax1(pairs * tpb * tpb), cnt), blk, st, a, L, c->D.lk, b, step);
       }
     } else
     for (int ib = LB; ib < a.nnmax; ib += LB) {
@@ -988,14 +1005,22 @@ static int fp_check(csp_ctx* c, int which, const double* x, hipStream_t st) {
   return 0;
 }
 
-void prep_lk(csp_ctx* c, const double* L, hipStream_t st) {
+// every large front of the tree sits in the last level and is of the k_top_chol class (a root alone, the tops of a demoted
+// level ...): a Cholesky that is followed by the inverse-form factor of the same matrix can leave Li behind in its launch
+static bool top_li_whole(csp_ctx* c) {
+  if (use_generic(c) || !use_large() || !c->D.gp_tptr || !c->D.nII_total || c->lvl.empty()) return false;
+  const LevelClass& Lc = c->lvl.back();
+  return c->D.nII_total == Lc.nII && use_top(Lc.nnmaxII + Lc.namaxII);
+}
+// have_li: Li of the large fronts is in D.lk already (cholesky_impl with li_last on this very matrix, top_li_whole)
+void prep_lk(csp_ctx* c, const double* L, hipStream_t st, bool have_li = false) {
   TreeArgs t = tree_args(c);
   if (use_large()) {
     t.lev = c->D.lev3idx;
     MfmaArgs a0 = mfma_args(c, nullptr, 0, 1);
     {
       Fork f(c, st, 0);          // the blocked inversions of the large fronts run beside the small cliques' launch
-      for_all_large(c, a0, [&](MfmaArgs am, int cnt) { lf_prep(c, am, cnt, L, f.s); });
+      for_all_large(c, a0, [&](MfmaArgs am, int cnt) { lf_prep(c, am, cnt, L, f.s, have_li); });
       if (c->D.nI_total) {
         int nnI = 0;
         for (const LevelClass& Lc : c->lvl) if (Lc.nI) nnI = std::max(nnI, (int)Lc.nnmaxI);
@@ -2748,13 +2773,13 @@ int csp_device_init(csp_ctx* c, int device, int64_t max_rhs) {
 
 int64_t csp_device_bytes(const csp_ctx* c) { return c ? c->D.bytes : 0; }
 
-static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set);
+static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set, bool li_last = false);
 int csp_cholesky(csp_ctx* c, double* x, void* stream) { return cholesky_impl(c, x, stream, 0); }
 int csp_cholesky_part(csp_ctx* c, double* x, int set, void* stream) {
   if (set < 1 || set > 2 || !c || !c->sets[set].lev2 || use_generic(c)) return SMCP_EINVAL;
   return cholesky_impl(c, x, stream, set);
 }
-static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set) {
+static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set, bool li_last) {
   if (int rc = ready(c)) return rc;
   invalidate_tags(c, x);
   hipStream_t st = (hipStream_t)stream;
@@ -2767,7 +2792,7 @@ static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set) {
       for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t bytes, int thr) {
         if (lds) launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)),
                             (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double), st, am, x, (double*)nullptr);   // compact layout: front + update only
-        else if (use_large() && c->D.gp_tptr) lf_chol(c, am, cnt, x, st);
+        else if (use_large() && c->D.gp_tptr) lf_chol(c, am, cnt, x, st, li_last && l == c->S.nlev - 1);
         else launch_lds(c, KID_chol_mfma_hbm, k_chol_mfma<false>, dim3(cnt), dim3(thr), 0, st, am, x, (double*)nullptr);
       }, set);
   } else
@@ -2809,13 +2834,13 @@ int csp_llt(csp_ctx* c, double* x, void* stream) {
   return 0;
 }
 
-static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set);
+static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set, bool have_li = false);
 int csp_projected_inverse(csp_ctx* c, double* x, void* stream) { return projected_inverse_impl(c, x, stream, 0); }
 int csp_projected_inverse_part(csp_ctx* c, double* x, int set, void* stream) {
   if (set < 1 || set > 2 || !c || !c->sets[set].lev2 || use_generic(c)) return SMCP_EINVAL;
   return projected_inverse_impl(c, x, stream, set);
 }
-static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set) {
+static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set, bool have_li) {
   if (int rc = ready(c)) return rc;
   invalidate_tags(c, x);
   hipStream_t st = (hipStream_t)stream;
@@ -2823,7 +2848,7 @@ static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set) 
   if (!use_generic(c)) {
     if (set) { prep_lk_set(c, set, x, st); c->D.lk_tag_L = nullptr; c->D.lk_tag_Y = nullptr; }   // partial: no cache claim
     else {
-    prep_lk(c, x, st);
+    prep_lk(c, x, st, have_li);
     c->D.lk_tag_L = nullptr;   // x is about to be overwritten by Y: LK stays valid for the pair (L, Y = x)
     c->D.lk_tag_Y = x;
     }
@@ -2897,9 +2922,12 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
   const bool fast = !use_generic(c) && use_large() && D.gp_tptr && !cache_off() && Fork::enabled() && scaling_overlap_on() &&
                     c->ntrial == 1 && lstar < S.nlev && (lstar > 0 || D.nI_total == 0) && D.yaa && S.updlen() > 0 && !c->verify_cache;
   if (!fast) {      // the three steps one after the other (any tree, any switch)
-    if (int rc = cholesky_impl(c, L, (void*)st, 0)) return rc;
+    const bool li = top_li_whole(c);        // (a root alone: its Li comes out of the Cholesky launch here as well)
+    // (D.lk changes from that launch on, also when the factorisation then fails: whatever was cached in it is gone)
+    if (li) { D.lk_tag_L = D.lk_tag_Y = nullptr; D.part_valid = false; D.lk_gen++; }
+    if (int rc = cholesky_impl(c, L, (void*)st, 0, li)) return rc;
     HIPCHK(hipMemcpyAsync(Y, L, sizeof(double) * bl, hipMemcpyDeviceToDevice, st));
-    if (int rc = projected_inverse_impl(c, Y, (void*)st, 0)) return rc;
+    if (int rc = projected_inverse_impl(c, Y, (void*)st, 0, li)) return rc;
     c->D.lk_tag_L = L;                      // L itself is intact: LK is its inverse form as well as the pair's
     if (flags & SCALING_FAC) { if (int rc = prepare_yaa(c, Y, true, st)) return rc; HIPCHK(end_call(c)); }
     return 0;
@@ -2925,7 +2953,7 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
       const size_t lb = (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double);
       if (lds && fuse_prep) launch_lds(c, KID_chol_mfma, k_chol_mfma<true, true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, D.lk);
       else if (lds) launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, (double*)nullptr);
-      else lf_chol(c, am, cnt, L, st);
+      else lf_chol(c, am, cnt, L, st, l == last);      // (the last level's chain: Li in the same launch where the class allows)
     });
   };
   // ---- 1. cholesky, leaves -> root.  Every cross-stream dependency costs ~10 us of idle stream on this stack (rocprofv3
@@ -2948,7 +2976,7 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
     for_level_classes(c, ll, a0, [&](bool lds, MfmaArgs am, int cnt, size_t, int) { if (!lds) lf_prep(c, am, cnt, L, s0); });
   if (tail0 > 0) (void)hipMemcpyAsync(Y, L, sizeof(double) * tail0, hipMemcpyDeviceToDevice, s0);
   // ---- 2. the last level's inverse form and the tail of Y on the caller's stream, then the side branch is joined
-  for_level_classes(c, last, a0, [&](bool lds, MfmaArgs am, int cnt, size_t, int) { if (!lds) lf_prep(c, am, cnt, L, st); });
+  for_level_classes(c, last, a0, [&](bool lds, MfmaArgs am, int cnt, size_t, int) { if (!lds) lf_prep(c, am, cnt, L, st, use_top(am.nnmax + am.namax)); });
   (void)hipMemcpyAsync(Y + tail0, L + tail0, sizeof(double) * (bl - tail0), hipMemcpyDeviceToDevice, st);
   if (f0) f0->join();
   D.lk_gen++;

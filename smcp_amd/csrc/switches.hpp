@@ -28,6 +28,7 @@ static const Switch SWITCHES[] = {
   {"SMCP_CHOL_PREP", "1", "0: k_prep_lk in a launch of its own instead of inside k_chol_mfma (narrow supernodes)"},
   {"SMCP_FAC_PARTIAL", "1", "0: chol(Y_AA) of the family children always formed by the fused scaling point"},
   {"SMCP_MID", "1", "0: per-step kernels instead of k_mid_chol / k_lf_diag_inv for fronts of at most 272 rows"},
+  {"SMCP_TOP_FUSED", "1", "0: k_mid_chol, and k_lf_diag_inv / k_lf_trtri for the inverse at the scaling point, instead of the register-resident k_top_chol for fronts of at most 208 rows"},
   {"SMCP_TRTRI", "1", "0: block-row triangular inversion of large fronts instead of recursive doubling"},
   {"SMCP_N16", "1", "0: no shape-specialised k_hess_up_n16"},
   {"SMCP_OLDLDS", "0", "1: k_hess_up_mfma<true> instead of the padded / n16 kernels"},
