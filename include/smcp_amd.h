@@ -127,6 +127,19 @@ int csp_hessian(csp_ctx* ctx, const double* L, const double* Y, double* U, int64
  * with rows in the permuted (symbolic) order; trans 0: L^-1 B, 1: L^-T B. */
 int csp_trsm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb, int trans,
              void* stream);
+/* chompack.trmm(L, B, alpha, trans): B <- alpha L B (trans 0) or alpha L^T B (trans != 0), L read as a lower-triangular
+ * factor (what csp_cholesky / csp_completion leave: of the diagonal block of a supernode only the lower triangle counts).
+ * B has the layout of csp_trsm: a dense n x nrhs column-major matrix with leading dimension ldb >= n, rows in the
+ * permuted (symbolic) order; entries between n and ldb of a column are not touched.  L is not changed and nothing cached
+ * for it is dropped.  alpha is applied once, at the last write.  Two or three kernel launches whatever the depth of the
+ * clique tree (the products of all cliques at once, then one combining pass).  Deterministic on every route: the
+ * contributions to an entry are summed in a fixed order, there are no floating-point atomics, and the same arguments
+ * give the same bits from call to call.  Does not synchronise: the work is queued on `stream`, the return value reports
+ * launch failures only.  Needs sepptr[nsn] * nrhs doubles of update workspace for trans 0 (SMCP_ENOMEM otherwise: call
+ * csp_device_init with a larger max_rhs, as chordal.trmm does).  SMCP_EINVAL for nrhs < 1 or above 2^18, ldb < n, or a
+ * context under a subtree partition over more than one rank (csp_set_partition). */
+int csp_trmm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans,
+             void* stream);
 /* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
  * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
  * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */

@@ -239,6 +239,22 @@ def trsm(L, B, trans="N"):
                              1 if trans in ("T", 1, True) else 0, _stream()), "trsm")
 
 
+def trmm(L, B, alpha=1.0, trans="N"):
+    """chompack.trmm(L, B, alpha, trans): B <- alpha L B ('N') or alpha L^T B ('T'; also 1, True), with L read as a
+    lower-triangular factor (as ``cholesky`` / ``completion`` leave it) and B laid out as for ``trsm``: a float64 device
+    tensor of shape (k, n) with stride(1) == 1 whose row r is column r of B, rows in the PERMUTED order; the entries
+    B[r, n:stride(0)] of a padded tensor are not touched.  L is not changed.  Two or three launches whatever the tree, and
+    the same arguments give the same bits from call to call (csp_trmm)."""
+    symb = L.symb
+    _ensure(symb)
+    assert B.dim() == 2 and B.stride(1) == 1 and B.shape[1] == symb.n
+    need = -(-int(symb.sepptr[-1]) * B.shape[0] // max(1, 2 * symb.blklen))
+    if symb._max_rhs < need:
+        symb.device_init(symb._device, need)
+    _chk(_lib.lib().csp_trmm(symb.handle, L.blkval.data_ptr(), B.data_ptr(), B.shape[0], B.stride(0), float(alpha),
+                             1 if trans in ("T", 1, True) else 0, _stream()), "trmm")
+
+
 def dot(X, Y):
     _ensure(X.symb)
     out = ctypes.c_double(0.0)

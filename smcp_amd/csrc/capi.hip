@@ -35,6 +35,7 @@
 #include "front_mrc.hip"
 #include "front_edm.hip"
 #include "front_psd.hip"
+#include "front_trmm.hip"
 
 using namespace smcp;
 
@@ -68,6 +69,7 @@ enum {
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
   KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
   KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill, KID_top_chol, KID_lf_trtri,
+  KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -88,7 +90,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_stack_trsm", "k_stack_dots", "k_stack_comb", "k_qr_small", "k_fam2_prep", "k_mid_chol", "k_lf_diag_inv", "k_lfsp_up", "k_lfsp_prep", "k_leaf_pairs", "k_leaf_tables", "k_fam_sparse", "k_gram_diag128", "k_lf_assemble_lds", "k_fam_terms", "k_famt_prep", "k_lf_assemble_lds_dyn", "k_lf_zsp", "k_fam_terms_grp", "k_lf_assemble_fz", "k_factor_inverse_lds", "k_chol_flow",
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
   "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
-  "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri"};
+  "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri",
+  "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2285,7 +2288,8 @@ void csp_symbolic_destroy(csp_ctx* c) {
     void* ptrs[] = {D.lfsp_skip, D.famt_skip, D.both_skip, D.trsm_x, D.fp, D.fp_bad, D.gsl_start, D.gsl_len, D.lg_list, D.lg_slot, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.sp_rt, D.sp_mk, D.lfsp_list, D.faci, D.lfd, D.lev3idx, D.updp, D.gp_tptr, D.gp_tgt, D.gp_cptr, D.gp_src, D.sw, D.gpart, D.lev2idx, D.lk, D.cl, D.rowidx, D.relidx, D.chidx, D.levidx, D.upd, D.yaa, D.fac, D.tmp, D.tmpptr,
                     D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
                     D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
-                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra};
+                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra,
+                    D.trmm_tptr, D.trmm_pos, D.trmm_heavy, D.trmm_items[0], D.trmm_items[1], D.trmm_tiles[0], D.trmm_tiles[1]};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
@@ -3187,6 +3191,138 @@ int csp_trsm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, 
   if (int rc = ready(c)) return rc;
   if (nrhs < 1 || ldb < c->S.n) return SMCP_EINVAL;
   return trsm_impl(c, L, nullptr, B, nrhs, ldb, trans, (hipStream_t)stream);
+}
+
+// ---- products with the factor (front_trmm.hip) ----------------------------------------------------------------------
+// Once per context: the transposed separator index (specified by the numpy restatement of tests/trmm_ref.py: position p
+// of its lists (tk, tq) is pos[sepptr[tk[p]] + tq[p]] here), the item lists of the FMA kernels and the row tiles of the
+// tile products.
+static int trmm_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  if (D.trmm_tptr) return 0;
+  const Symbolic& S = c->S;
+  if (S.sepptr[S.nsn] >= ((int64_t)1 << 31)) return SMCP_EINVAL;      // positions are 32-bit
+  std::vector<int64_t> tptr((size_t)S.n + 1, 0);
+  for (int64_t k = 0; k < S.nsn; ++k)
+    for (int64_t q = 0; q < S.na(k); ++q) ++tptr[(size_t)S.rowidx[S.rowptr[k] + S.nn(k) + q] + 1];
+  for (int64_t i = 0; i < S.n; ++i) tptr[(size_t)i + 1] += tptr[(size_t)i];
+  std::vector<int32_t> pos((size_t)S.sepptr[S.nsn]);
+  {
+    std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
+    for (int64_t k = 0; k < S.nsn; ++k)           // ascending k: the order of the sums of k_trmm_combine
+      for (int64_t q = 0; q < S.na(k); ++q) pos[(size_t)(S.sepptr[k] + q)] = (int32_t)fill[(size_t)S.rowidx[S.rowptr[k] + S.nn(k) + q]]++;
+  }
+  std::vector<int32_t> heavy;
+  for (int64_t i = 0; i < S.n; ++i) if (tptr[(size_t)i + 1] - tptr[(size_t)i] > TRMM_HEAVY) heavy.push_back((int32_t)i);
+  // items: the cliques outside the large class, then the large fronts; for N every group is padded to whole workgroups
+  // (clique -1) and the row chunks of wide supernodes come last, four items (the parts of the k range) each
+  std::vector<int32_t> items[2];
+  int64_t nsmall[2] = {0, 0};
+  auto pad = [&]() { while ((items[0].size() / 2) % TRMM_WAVES) { items[0].push_back(-1); items[0].push_back(0); } };
+  for (int pass = 0; pass < 3; ++pass) {          // N: small, large, split
+    for (int64_t k = 0; k < S.nsn; ++k) {
+      const bool large = c->large_mask[(size_t)k] != 0, split = large && S.nn(k) >= TRMM_SPLIT_NN;
+      if (pass != (split ? 2 : large ? 1 : 0)) continue;
+      for (int64_t ch = 0; ch < (S.nf(k) + 63) / 64; ++ch)
+        for (int part = 0; part < (split ? TRMM_WAVES : 1); ++part) { items[0].push_back((int32_t)k); items[0].push_back(trmm_code((int)ch, part, split ? 1 : 0)); }
+    }
+    pad();
+    if (pass == 0) nsmall[0] = (int64_t)items[0].size() / 2;
+  }
+  for (int pass = 0; pass < 2; ++pass) {          // T: small, large
+    for (int64_t k = 0; k < S.nsn; ++k) {
+      if ((c->large_mask[(size_t)k] != 0) != (pass == 1)) continue;
+      for (int64_t ch = 0; ch < (S.nn(k) + TRMM_JC - 1) / TRMM_JC; ++ch) { items[1].push_back((int32_t)k); items[1].push_back((int32_t)ch); }
+    }
+    if (pass == 0) nsmall[1] = (int64_t)items[1].size() / 2;
+  }
+  // row tiles of the tile products: the large fronts first (the long tiles start first), widest front first among them
+  std::vector<int32_t> tiles[2];
+  int64_t nlarge[2] = {0, 0};
+  {
+    std::vector<int64_t> order;
+    for (int pass = 1; pass >= 0; --pass)
+      for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
+    std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
+    for (size_t x = 0; x < order.size(); ++x) {
+      const int64_t k = order[x];
+      for (int t = 0; t < 2; ++t) {
+        for (int64_t rt = 0; rt < tiles64((int)(t ? S.nn(k) : S.nf(k))); ++rt) { tiles[t].push_back((int32_t)k); tiles[t].push_back((int32_t)rt); }
+        if ((int64_t)x + 1 == D.nII_total) nlarge[t] = (int64_t)tiles[t].size() / 2;
+      }
+    }
+  }
+  int rc = 0;
+  if ((rc = dev_upload(&D.trmm_pos, pos, D.bytes))) return rc;
+  for (int t = 0; t < 2; ++t) {
+    if ((rc = dev_upload(&D.trmm_tiles[t], tiles[t], D.bytes))) return rc;
+    D.trmm_ntiles[t][0] = nlarge[t];
+    D.trmm_ntiles[t][1] = (int64_t)tiles[t].size() / 2;
+  }
+  if ((rc = dev_upload(&D.trmm_heavy, heavy, D.bytes))) return rc;
+  D.trmm_nheavy = (int64_t)heavy.size();
+  for (int t = 0; t < 2; ++t) {
+    if ((rc = dev_upload(&D.trmm_items[t], items[t], D.bytes))) return rc;
+    D.trmm_nitems[t][0] = nsmall[t];
+    D.trmm_nitems[t][1] = (int64_t)items[t].size() / 2;
+  }
+  return dev_upload(&D.trmm_tptr, tptr, D.bytes);
+}
+
+int trmm_impl(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans, hipStream_t st) {
+  static const int mm = sw_int("SMCP_TRMM_MM", 1);
+  DeviceCtx& D = c->D;
+  const Symbolic& S = c->S;
+  if (int rc = trmm_setup(c)) return rc;
+  if (!trans && S.sepptr[S.nsn] * nrhs > D.max_rhs * D.tmplen) return SMCP_ENOMEM;
+  const int64_t need = ldb * nrhs;
+  if (D.trsm_x_len < need) {      // the scratch image of B is csp_trsm's: neither call keeps it
+    if (D.trsm_x) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(D.trsm_x)); D.bytes -= D.trsm_x_len * 8; D.trsm_x = nullptr; D.trsm_x_len = 0; }
+    if (int rc = dev_alloc(&D.trsm_x, need, D.bytes)) return rc;
+    D.trsm_x_len = need;
+  }
+  // tile products for the large fronts from eight columns on (the gate of csp_trsm) and for every front from TRMM_MM_ALL
+  // columns on; everything else, and everything on the generic / deterministic route, on the FMA kernels
+  const bool mm_ok = mm && !use_generic(c) && use_large();
+  const bool tiles_all = mm_ok && mm != 2 && nrhs >= TRMM_MM_ALL;
+  const bool tiles = tiles_all || (mm_ok && nrhs >= 8 && D.nII_total > 0);
+  TrmmArgs a;
+  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.trmm_items[trans];
+  a.nitems = tiles_all ? 0 : (int)D.trmm_nitems[trans][tiles ? 0 : 1];
+  a.tiles = D.trmm_tiles[trans];
+  a.L = L; a.B = B; a.X = D.trsm_x; a.U = D.tmp; a.pos = D.trmm_pos; a.ntot = S.sepptr[S.nsn]; a.nrhs = (int)nrhs; a.ldb = ldb;
+  auto fma = [&](auto cb) {        // CB columns of B per wave: L is read once per block of CB columns
+    constexpr int CB = decltype(cb)::value;
+    const dim3 grid((unsigned)((a.nitems + TRMM_WAVES - 1) / TRMM_WAVES), (unsigned)((a.nrhs + CB - 1) / CB));
+    if (!trans) launch(c, KID_trmm_n, k_trmm_n<CB>, grid, dim3(64 * TRMM_WAVES), st, a);
+    else launch(c, KID_trmm_t, k_trmm_t<CB>, grid, dim3(64 * TRMM_WAVES), st, a);
+  };
+  if (a.nitems) {
+    if (nrhs == 1) fma(std::integral_constant<int, 1>{});
+    else if (nrhs <= 4) fma(std::integral_constant<int, 4>{});
+    else fma(std::integral_constant<int, 8>{});
+  }
+  if (tiles) {
+    const dim3 grid((unsigned)D.trmm_ntiles[trans][tiles_all ? 1 : 0], (unsigned)tiles64((int)nrhs));
+    if (!trans) launch(c, KID_trmm_mm, k_trmm_mm<false>, grid, dim3(256), st, a);
+    else launch(c, KID_trmm_mm, k_trmm_mm<true>, grid, dim3(256), st, a);
+  }
+  {
+    const int64_t cap = 16 * (int64_t)D.ncu;
+    const int light = (int)std::min<int64_t>((S.n * nrhs + 255) / 256, cap);
+    const int64_t nheavy = trans ? 0 : D.trmm_nheavy;
+    const int hw = (int)std::min<int64_t>((nheavy * nrhs + 3) / 4, cap);
+    launch(c, KID_trmm_combine, k_trmm_combine, dim3((unsigned)(light + hw)), dim3(256), st, (const int64_t*)(trans ? nullptr : D.trmm_tptr),
+           (const int32_t*)D.trmm_heavy, (int)nheavy, light, (const double*)D.trsm_x, (const double*)D.tmp, a.ntot, B, S.n, (int)nrhs, ldb, alpha);
+  }
+  HIPCHK(end_call(c));
+  return 0;
+}
+int csp_trmm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans, void* stream) {
+  if (int rc = ready(c)) return rc;
+  // (grid limits of the column-block dimension; a partitioned context holds valid factors on its own cliques only)
+  if (nrhs < 1 || nrhs > ((int64_t)1 << 18) || ldb < c->S.n || c->xr_world > 1) return SMCP_EINVAL;
+  return trmm_impl(c, L, B, nrhs, ldb, alpha, trans ? 1 : 0, (hipStream_t)stream);
 }
 
 // ---- minimum-rank completion (front_mrc.hip) ----------------------------------------------------------------------

@@ -111,7 +111,7 @@ struct DeviceCtx {
   int64_t fam_maxterms = 0;  // most entries of a (family, constraint) pair: the parent's own + its children's
   double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
   double* vbuf = nullptr;    // n x vcols : S^-1[:, K_s] of the chunk in flight
-  double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route)
+  double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
   int64_t vcols = 0;
   double* hd = nullptr;      // md x md Gram block of the dense constraints (when ns > 0)
   // blocked dense Cholesky of the Schur complement: inverses of its 64 x 64 diagonal blocks (for the blocked potrs)
@@ -165,6 +165,15 @@ struct DeviceCtx {
   // W_k[rho] (at its panel offset), the rows A[rho] (at its separator offset) and |rho|
   struct PsdTask* psd_tasks = nullptr; int32_t* psd_ulist = nullptr;
   double* psd_w = nullptr; int32_t* psd_idx = nullptr; int32_t* psd_ra = nullptr;
+  // products with the factor (front_trmm.hip): the transposed separator index (row i of the matrix owns the positions
+  // [trmm_tptr[i], trmm_tptr[i + 1]) of a list of all separator entries, its own in ascending clique; trmm_pos[sepptr[k] + q] =
+  // the position of entry q of clique k), the rows with more than TRMM_HEAVY entries, and the (clique, chunk) items of the FMA
+  // kernels, per trans: the items of the large fronts come last ([t][0]: items without them, [t][1]: all); the (clique, row
+  // tile) pairs of the tile products, per trans: those of the large fronts come FIRST ([t][0]: theirs, [t][1]: all)
+  int64_t* trmm_tptr = nullptr; int32_t* trmm_pos = nullptr;
+  int32_t* trmm_heavy = nullptr; int64_t trmm_nheavy = 0;
+  int32_t* trmm_items[2] = {nullptr, nullptr}; int64_t trmm_nitems[2][2] = {{0, 0}, {0, 0}};
+  int32_t* trmm_tiles[2] = {nullptr, nullptr}; int64_t trmm_ntiles[2][2] = {{0, 0}, {0, 0}};
   int64_t bytes = 0;
 };
 
