@@ -140,6 +140,21 @@ int csp_trsm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb
  * context under a subtree partition over more than one rank (csp_set_partition). */
 int csp_trmm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans,
              void* stream);
+/* chompack.syr2(X, y, z, alpha, beta) for a block of k columns: X <- beta X + alpha P_V(U V^T + V U^T), or, with V == NULL,
+ * X <- beta X + alpha P_V(U U^T) (ldv is then ignored).  U and V have the layout of csp_trsm: dense n x k column-major
+ * matrices with leading dimensions ldu, ldv >= n, rows in the permuted (symbolic) order; they are never written, and V may
+ * alias U (the result is then 2 alpha P_V(U U^T), computed as the rank-2k update).  For clique c with columns N, front rows
+ * F = [N; A] and its nf x nn panel, panel[m, j] = beta panel[m, j] + alpha sum_r (U[F_m, r] V[N_j, r] + V[F_m, r] U[N_j, r])
+ * on the rows m >= j of the N N part and all rows of the A N part, r ascending.  The call writes EVERY slot of X (blklen
+ * doubles): the slots outside the pattern, the strict upper triangles of the N N blocks, are never read and are stored as
+ * exactly 0.0.  beta == 0: X is not read (NaN / Inf in it do not propagate); alpha == 0: U and V are not read.  X is read
+ * once and written once, every entry has one owner and a fixed order of summation: no atomics, and the same arguments
+ * give the same bits from call to call.  One or two kernel launches whatever the clique tree.  Whatever the library had
+ * derived from the old contents at X's address is dropped.  Does not synchronise: the work is queued on `stream`, the
+ * return value reports launch failures only.  SMCP_EINVAL for k < 1 or above 2^18, ldu < n, ldv < n (V given), or a
+ * context under a subtree partition over more than one rank (csp_set_partition). */
+int csp_syr2k(csp_ctx* ctx, double* X, const double* U, const double* V, int64_t k, int64_t ldu, int64_t ldv, double alpha,
+              double beta, void* stream);
 /* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
  * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
  * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */

@@ -255,6 +255,55 @@ def trmm(L, B, alpha=1.0, trans="N"):
                              1 if trans in ("T", 1, True) else 0, _stream()), "trmm")
 
 
+def _dense_block(symb, B, what):
+    assert B.dim() == 2 and B.stride(1) == 1 and B.shape[1] == symb.n and B.shape[0] >= 1, what
+    assert B.shape[0] == 1 or B.stride(0) >= symb.n, what
+    assert B.dtype == torch.float64, what
+    return B.stride(0) if B.shape[0] > 1 else max(B.stride(0), symb.n)
+
+
+def syr2k(X, U, V, alpha=1.0, beta=1.0):
+    """X <- beta X + alpha P_V(U V^T + V U^T), in place: the rank-2k form of chompack.syr2.  U and V are dense n x k blocks
+    laid out as for ``trsm`` / ``trmm``: float64 device tensors of shape (k, n) with stride(1) == 1 and stride(0) >= n whose
+    row r is column r of the block, rows in the PERMUTED order.  They are not written; V may be U.  Every slot of X.blkval is
+    written (those outside the pattern as exactly 0.0), X is not read when beta == 0, U and V are not read when alpha == 0,
+    and the same arguments give the same bits from call to call.  One or two launches whatever the tree (csp_syr2k)."""
+    symb = X.symb
+    ldu = _dense_block(symb, U, "U")
+    ldv = _dense_block(symb, V, "V")
+    assert U.shape[0] == V.shape[0]
+    assert U.is_cuda and V.is_cuda
+    _ensure(symb)
+    X.touched()
+    try:
+        _chk(_lib.lib().csp_syr2k(symb.handle, X.blkval.data_ptr(), U.data_ptr(), V.data_ptr(), U.shape[0], ldu, ldv,
+                                  float(alpha), float(beta), _stream()), "syr2k")
+    finally:
+        note_cache(symb, X)
+
+
+def syrk(X, U, alpha=1.0, beta=1.0):
+    """X <- beta X + alpha P_V(U U^T), in place, for U as in ``syr2k``: P_V(Y Y^T) of a low-rank factor (the Y of
+    ``mrcompletion`` as ``Y.t().contiguous()``) without an n x n intermediate."""
+    symb = X.symb
+    ldu = _dense_block(symb, U, "U")
+    assert U.is_cuda
+    _ensure(symb)
+    X.touched()
+    try:
+        _chk(_lib.lib().csp_syr2k(symb.handle, X.blkval.data_ptr(), U.data_ptr(), None, U.shape[0], ldu, 0,
+                                  float(alpha), float(beta), _stream()), "syrk")
+    finally:
+        note_cache(symb, X)
+
+
+def syr2(X, y, z, alpha=1.0, beta=1.0):
+    """chompack.syr2(X, y, z, alpha, beta): X <- beta X + alpha P_V(y z^T + z y^T) for 1-D float64 device tensors y, z of
+    length n in the PERMUTED order (``syr2k`` with k = 1)."""
+    assert y.dim() == 1 and z.dim() == 1
+    syr2k(X, y.unsqueeze(0), z.unsqueeze(0), alpha, beta)
+
+
 def dot(X, Y):
     _ensure(X.symb)
     out = ctypes.c_double(0.0)

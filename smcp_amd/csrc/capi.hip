@@ -36,6 +36,7 @@
 #include "front_edm.hip"
 #include "front_psd.hip"
 #include "front_trmm.hip"
+#include "front_syr2k.hip"
 
 using namespace smcp;
 
@@ -69,7 +70,7 @@ enum {
   KID_mrc_diag, KID_mrc_rank, KID_mrc_reduce, KID_mrc_factor, KID_cut_signs, KID_cut_weights,
   KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
   KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill, KID_top_chol, KID_lf_trtri,
-  KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine,
+  KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine, KID_syr2k_fma, KID_syr2k_mm,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -91,7 +92,7 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
   "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
   "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri",
-  "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine"};
+  "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2289,7 +2290,8 @@ void csp_symbolic_destroy(csp_ctx* c) {
                     D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
                     D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
                     D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra,
-                    D.trmm_tptr, D.trmm_pos, D.trmm_heavy, D.trmm_items[0], D.trmm_items[1], D.trmm_tiles[0], D.trmm_tiles[1]};
+                    D.trmm_tptr, D.trmm_pos, D.trmm_heavy, D.trmm_items[0], D.trmm_items[1], D.trmm_tiles[0], D.trmm_tiles[1],
+                    D.syr2k_items, D.syr2k_tiles};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
@@ -3323,6 +3325,83 @@ int csp_trmm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, 
   // (grid limits of the column-block dimension; a partitioned context holds valid factors on its own cliques only)
   if (nrhs < 1 || nrhs > ((int64_t)1 << 18) || ldb < c->S.n || c->xr_world > 1) return SMCP_EINVAL;
   return trmm_impl(c, L, B, nrhs, ldb, alpha, trans ? 1 : 0, (hipStream_t)stream);
+}
+
+// ---- rank-k updates projected on the pattern (front_syr2k.hip) ------------------------------------------------------
+// Once per context: the item list of the FMA kernel and the tile list of the tile products.
+static int syr2k_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  if (D.syr2k_ready) return 0;
+  const Symbolic& S = c->S;
+  std::vector<int32_t> items, tiles;
+  auto list = [&](std::vector<int32_t>& out, int64_t k, int rows, int cols) {       // computing entries, then the zero-only ones
+    const int64_t nf = S.nf(k), nn = S.nn(k);
+    for (int zero = 0; zero < 2; ++zero)
+      for (int64_t r = 0; r < (nf + rows - 1) / rows; ++r)
+        for (int64_t j = 0; j < (nn + cols - 1) / cols; ++j) {
+          const bool above = std::min<int64_t>(r * rows + rows, nf) - 1 < j * cols;   // the last row lies above the first column
+          if (above == (zero == 1)) { out.push_back((int32_t)k); out.push_back((int32_t)r); out.push_back((int32_t)j); out.push_back(zero); }
+        }
+  };
+  for (int pass = 0; pass < 2; ++pass) {          // items: small, large
+    for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) list(items, k, 64, SYR2K_JC);
+    D.syr2k_nitems[pass] = (int64_t)items.size() / 4;
+  }
+  {                                               // tiles: large (widest front first: the long tiles start first), small
+    std::vector<int64_t> order;
+    for (int pass = 1; pass >= 0; --pass)
+      for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
+    std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
+    for (size_t x = 0; x < order.size(); ++x) {
+      list(tiles, order[x], LT, LT);
+      if ((int64_t)x + 1 == D.nII_total) D.syr2k_ntiles[0] = (int64_t)tiles.size() / 4;
+    }
+    D.syr2k_ntiles[1] = (int64_t)tiles.size() / 4;
+  }
+  if (D.syr2k_nitems[1] >= ((int64_t)1 << 31) || D.syr2k_ntiles[1] >= ((int64_t)1 << 31)) return SMCP_EINVAL;     // grid dimension
+  if (int rc = dev_upload(&D.syr2k_items, items, D.bytes)) return rc;
+  if (int rc = dev_upload(&D.syr2k_tiles, tiles, D.bytes)) return rc;
+  D.syr2k_ready = true;
+  return 0;
+}
+
+int csp_syr2k(csp_ctx* c, double* X, const double* U, const double* V, int64_t k, int64_t ldu, int64_t ldv, double alpha, double beta,
+              void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int mm = sw_int("SMCP_SYR2K_MM", 1);      // read on every call: tools/syr2k_time.py alternates the settings in one process
+  // (the inner dimension 2k is an int; a partitioned context keeps valid panels on its own cliques only)
+  if (k < 1 || k > ((int64_t)1 << 18) || ldu < c->S.n || (V && ldv < c->S.n) || c->xr_world > 1) return SMCP_EINVAL;
+  if (int rc = syr2k_setup(c)) return rc;
+  DeviceCtx& D = c->D;
+  hipStream_t st = (hipStream_t)stream;
+  invalidate_tags(c, X);
+  // tile products for the large fronts from SYR2K_MM_LARGE ranks on and for every front from SYR2K_MM_ALL ranks on; everything
+  // else, and everything on the generic / deterministic route, on the FMA kernel
+  const bool mm_ok = mm && !use_generic(c) && use_large();
+  const bool tiles_all = mm_ok && mm != 2 && k >= SYR2K_MM_ALL;
+  const bool tiles = tiles_all || (mm_ok && k >= SYR2K_MM_LARGE && D.nII_total > 0);
+  Syr2kArgs a;
+  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.syr2k_items; a.tiles = D.syr2k_tiles;
+  a.nitems = tiles_all ? 0 : (int)D.syr2k_nitems[tiles ? 0 : 1];
+  a.X = X; a.U = U; a.V = V; a.k = (int)k; a.ldu = ldu; a.ldv = V ? ldv : ldu; a.alpha = alpha; a.beta = beta;
+  auto fma_launch = [&](auto rb) {
+    constexpr int RB = decltype(rb)::value;
+    const dim3 grid((unsigned)((a.nitems + SYR2K_WAVES - 1) / SYR2K_WAVES));
+    if (V) launch(c, KID_syr2k_fma, k_syr2k_fma<RB, true>, grid, dim3(64 * SYR2K_WAVES), st, a);
+    else launch(c, KID_syr2k_fma, k_syr2k_fma<RB, false>, grid, dim3(64 * SYR2K_WAVES), st, a);
+  };
+  if (a.nitems) {
+    if (k == 1) fma_launch(std::integral_constant<int, 1>{});
+    else if (k <= 4) fma_launch(std::integral_constant<int, 4>{});
+    else fma_launch(std::integral_constant<int, 8>{});
+  }
+  const int64_t ntiles = tiles ? D.syr2k_ntiles[tiles_all ? 1 : 0] : 0;
+  if (ntiles) {
+    if (V) launch(c, KID_syr2k_mm, k_syr2k_mm<true>, dim3((unsigned)ntiles), dim3(256), st, a);
+    else launch(c, KID_syr2k_mm, k_syr2k_mm<false>, dim3((unsigned)ntiles), dim3(256), st, a);
+  }
+  HIPCHK(end_call(c));
+  return 0;
 }
 
 // ---- minimum-rank completion (front_mrc.hip) ----------------------------------------------------------------------

@@ -174,6 +174,12 @@ struct DeviceCtx {
   int32_t* trmm_heavy = nullptr; int64_t trmm_nheavy = 0;
   int32_t* trmm_items[2] = {nullptr, nullptr}; int64_t trmm_nitems[2][2] = {{0, 0}, {0, 0}};
   int32_t* trmm_tiles[2] = {nullptr, nullptr}; int64_t trmm_ntiles[2][2] = {{0, 0}, {0, 0}};
+  // rank-k updates on the pattern (front_syr2k.hip): (clique, row chunk, column chunk, zero) items of the FMA kernel, those of
+  // the large fronts LAST ([0]: items without them, [1]: all), and (clique, row tile, column tile, zero) tiles of the tile
+  // products, those of the large fronts FIRST ([0]: theirs, [1]: all); zero: all rows above the diagonal, only zeros are stored
+  int32_t* syr2k_items = nullptr; int64_t syr2k_nitems[2] = {0, 0};
+  int32_t* syr2k_tiles = nullptr; int64_t syr2k_ntiles[2] = {0, 0};
+  bool syr2k_ready = false;
   int64_t bytes = 0;
 };
 
