@@ -155,6 +155,27 @@ int csp_trmm(csp_ctx* ctx, const double* L, double* B, int64_t nrhs, int64_t ldb
  * context under a subtree partition over more than one rank (csp_set_partition). */
 int csp_syr2k(csp_ctx* ctx, double* X, const double* U, const double* V, int64_t k, int64_t ldu, int64_t ldv, double alpha,
               double beta, void* stream);
+/* C <- alpha X B + beta C for the symmetric matrix X stored on the pattern and dense n x nrhs blocks B and C in the layout
+ * of csp_trsm (column-major, leading dimensions ldb, ldc >= n, rows in the permuted (symbolic) order).  X is read as a
+ * symmetric matrix: of the N N block of a supernode only the lower triangle counts, what is stored above it is never
+ * used.  X is never written and nothing cached for it is dropped.  B and the entries between n and the leading dimension
+ * of a column of B and of C are never written.  C must not overlap B: overlapping address ranges are SMCP_EINVAL.  A term
+ * whose factor is zero is left out, not multiplied by zero: beta == 0 does not read C (NaN / Inf there do not propagate),
+ * alpha == 0 reads neither X nor B and returns beta C (bit for bit for beta == 1), alpha == beta == 0 stores exact zeros.
+ * alpha and beta are applied once, in the last pass.  Two or three kernel launches whatever the clique tree: the partial
+ * products of all cliques at once (every stored entry of X is read once per block of columns and used for both of its
+ * outputs, row i and row j), stored through a contribution index built once per context, then one combining pass.  The
+ * order of every sum is fixed by that index: no floating-point atomics, and the same arguments give the same bits from
+ * call to call.  Does not synchronise: the work is queued on `stream`, the return value reports launch failures only.
+ * Needs csp_symm_positions(ctx) * nrhs doubles of update workspace (SMCP_ENOMEM otherwise: call csp_device_init with a
+ * larger max_rhs, as chordal.symm does).  SMCP_EINVAL for nrhs < 1 or above 2^18, ldb < n, ldc < n, or a context under a
+ * subtree partition over more than one rank (csp_set_partition); SMCP_ENODEV without a device. */
+int csp_symm(csp_ctx* ctx, const double* X, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t nrhs, double alpha,
+             double beta, void* stream);
+/* The number of partial products of one column of csp_symm (the length of its contribution index): one per row of every
+ * listed (clique, 64 panel rows, 256 panel columns) item and one per column of it with a row strictly below.  Host only:
+ * needs no device. */
+int64_t csp_symm_positions(csp_ctx* ctx);
 /* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
  * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
  * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */

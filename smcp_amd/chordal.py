@@ -304,6 +304,32 @@ def syr2(X, y, z, alpha=1.0, beta=1.0):
     syr2k(X, y.unsqueeze(0), z.unsqueeze(0), alpha, beta)
 
 
+def symm(X, B, C=None, alpha=1.0, beta=0.0):
+    """C <- alpha X B + beta C for the cspmatrix X read as a symmetric matrix (of the diagonal block of a supernode only the
+    lower triangle counts) and dense n x k blocks B, C laid out as for ``trsm`` / ``trmm`` / ``syr2k``: float64 device
+    tensors of shape (k, n) with stride(1) == 1 and stride(0) >= n whose row r is column r of the block, rows in the
+    PERMUTED order.  Returns C; ``C=None`` allocates a contiguous (k, n) tensor and needs beta == 0.  X and B are not
+    written, C must not overlap B, and a term whose factor is zero is left out: beta == 0 does not read C, alpha == 0
+    reads neither X nor B.  Nothing cached for X is dropped.  Two or three launches whatever the tree, and the same
+    arguments give the same bits from call to call (csp_symm)."""
+    symb = X.symb
+    ldb = _dense_block(symb, B, "B")
+    assert B.is_cuda
+    if C is None:
+        assert beta == 0, "C=None needs beta == 0"
+        C = torch.empty((B.shape[0], symb.n), dtype=torch.float64, device=B.device)
+    ldc = _dense_block(symb, C, "C")
+    assert C.is_cuda and C.shape[0] == B.shape[0]
+    _ensure(symb)
+    lib = _lib.lib()
+    need = -(-int(lib.csp_symm_positions(symb.handle)) * B.shape[0] // max(1, 2 * symb.blklen))
+    if symb._max_rhs < need:
+        symb.device_init(symb._device, need)
+    _chk(lib.csp_symm(symb.handle, X.blkval.data_ptr(), B.data_ptr(), ldb, C.data_ptr(), ldc, B.shape[0], float(alpha),
+                      float(beta), _stream()), "symm")
+    return C
+
+
 def dot(X, Y):
     _ensure(X.symb)
     out = ctypes.c_double(0.0)

@@ -37,6 +37,7 @@
 #include "front_psd.hip"
 #include "front_trmm.hip"
 #include "front_syr2k.hip"
+#include "front_symm.hip"
 
 using namespace smcp;
 
@@ -71,6 +72,7 @@ enum {
   KID_edm_rank, KID_edm_reduce, KID_edm_factor, KID_edm_dense, KID_hess_down_fam, KID_hess_up_fam1,
   KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill, KID_top_chol, KID_lf_trtri,
   KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine, KID_syr2k_fma, KID_syr2k_mm,
+  KID_symm_fma, KID_symm_mm, KID_symm_combine,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -92,7 +94,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_mrc_diag", "k_mrc_rank", "k_mrc_reduce", "k_mrc_factor", "k_cut_signs", "k_cut_weights",
   "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
   "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri",
-  "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm"};
+  "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm",
+  "k_symm_fma", "k_symm_mm", "k_symm_combine"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2291,7 +2294,7 @@ void csp_symbolic_destroy(csp_ctx* c) {
                     D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
                     D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra,
                     D.trmm_tptr, D.trmm_pos, D.trmm_heavy, D.trmm_items[0], D.trmm_items[1], D.trmm_tiles[0], D.trmm_tiles[1],
-                    D.syr2k_items, D.syr2k_tiles};
+                    D.syr2k_items, D.syr2k_tiles, D.symm_tptr, D.symm_pos, D.symm_heavy, D.symm_items};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
@@ -3399,6 +3402,151 @@ int csp_syr2k(csp_ctx* c, double* X, const double* U, const double* V, int64_t k
   if (ntiles) {
     if (V) launch(c, KID_syr2k_mm, k_syr2k_mm<true>, dim3((unsigned)ntiles), dim3(256), st, a);
     else launch(c, KID_syr2k_mm, k_syr2k_mm<false>, dim3((unsigned)ntiles), dim3(256), st, a);
+  }
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- products of the matrix itself with a dense block (front_symm.hip) -----------------------------------------------
+// The contribution index (specified by the numpy restatement of tests/symm_ref.py): the items (k, r, p) in ascending
+// order with the base of each in `pos`, row i of C owning the positions [tptr[i], tptr[i + 1]) with its partials in
+// ascending (k, side, r, p).  Host only; with tptr == nullptr it counts the positions and builds nothing.
+static int64_t symm_index(const Symbolic& S, std::vector<int64_t>* tptr, std::vector<int32_t>* pos, std::vector<int32_t>* items) {
+  int64_t ntot = 0;
+  if (tptr) tptr->assign((size_t)S.n + 1, 0);
+  auto each = [&](int64_t k, auto f) {            // f(r, p, rows of the chunk, columns with a column partial)
+    const int64_t nf = S.nf(k), nn = S.nn(k);
+    for (int64_t r = 0; r < (nf + SYMM_ROWS - 1) / SYMM_ROWS; ++r)
+      for (int64_t p = 0; p < (nn + SYMM_KP - 1) / SYMM_KP; ++p) {
+        const int64_t last = std::min<int64_t>(r * SYMM_ROWS + SYMM_ROWS, nf) - 1;
+        if (p * SYMM_KP > last) continue;         // the chunk lies above the diagonal of this part
+        f(r, p, last - r * SYMM_ROWS + 1, std::max<int64_t>(0, std::min(std::min<int64_t>(nn, p * SYMM_KP + SYMM_KP), last) - p * SYMM_KP));
+      }
+  };
+  for (int64_t k = 0; k < S.nsn; ++k)
+    each(k, [&](int64_t r, int64_t p, int64_t nrows, int64_t ncol) {
+      if (tptr) {
+        if (ntot < ((int64_t)1 << 31)) { items->push_back((int32_t)k); items->push_back((int32_t)r); items->push_back((int32_t)p); items->push_back((int32_t)ntot); }
+        for (int64_t j = 0; j < nrows; ++j) ++(*tptr)[(size_t)S.rowidx[S.rowptr[k] + r * SYMM_ROWS + j] + 1];
+        for (int64_t j = 0; j < ncol; ++j) ++(*tptr)[(size_t)(S.snptr[k] + p * SYMM_KP + j) + 1];
+      }
+      ntot += nrows + ncol;
+    });
+  if (!tptr || ntot >= ((int64_t)1 << 31)) return ntot;
+  for (int64_t i = 0; i < S.n; ++i) (*tptr)[(size_t)i + 1] += (*tptr)[(size_t)i];
+  pos->assign((size_t)ntot, 0);
+  std::vector<int64_t> fill(tptr->begin(), tptr->end() - 1);
+  size_t it0 = 0;
+  for (int64_t k = 0; k < S.nsn; ++k) {           // ascending (k, side, r, p): the order of the sums of k_symm_combine
+    size_t it = it0;
+    each(k, [&](int64_t r, int64_t, int64_t nrows, int64_t) {
+      const int64_t base = (*items)[4 * it + 3];
+      for (int64_t j = 0; j < nrows; ++j) (*pos)[(size_t)(base + j)] = (int32_t)fill[(size_t)S.rowidx[S.rowptr[k] + r * SYMM_ROWS + j]]++;
+      ++it;
+    });
+    it = it0;
+    each(k, [&](int64_t, int64_t p, int64_t nrows, int64_t ncol) {
+      const int64_t base = (*items)[4 * it + 3] + nrows;
+      for (int64_t j = 0; j < ncol; ++j) (*pos)[(size_t)(base + j)] = (int32_t)fill[(size_t)(S.snptr[k] + p * SYMM_KP + j)]++;
+      ++it;
+    });
+    it0 = it;
+  }
+  return ntot;
+}
+
+int64_t csp_symm_positions(csp_ctx* c) {
+  if (!c) return SMCP_EINVAL;
+  if (c->D.symm_ntot < 0) c->D.symm_ntot = symm_index(c->S, nullptr, nullptr, nullptr);
+  return c->D.symm_ntot;
+}
+
+// Once per context: the index on the device, the rows with more than SYMM_HEAVY partials, and the item list with the
+// large fronts first (the long items start first), the widest front first among them.
+static int symm_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  if (D.symm_tptr) return 0;
+  const Symbolic& S = c->S;
+  std::vector<int64_t> tptr;
+  std::vector<int32_t> pos, byk;
+  const int64_t ntot = symm_index(S, &tptr, &pos, &byk);
+  if (ntot >= ((int64_t)1 << 31)) return SMCP_EINVAL;                 // positions are 32-bit
+  D.symm_ntot = ntot;
+  std::vector<int32_t> heavy;
+  for (int64_t i = 0; i < S.n; ++i) if (tptr[(size_t)i + 1] - tptr[(size_t)i] > SYMM_HEAVY) heavy.push_back((int32_t)i);
+  std::vector<size_t> kfirst((size_t)S.nsn + 1, byk.size() / 4);
+  for (size_t it = byk.size() / 4; it-- > 0;) kfirst[(size_t)byk[4 * it]] = it;
+  for (int64_t k = S.nsn - 1; k >= 0; --k) kfirst[(size_t)k] = std::min(kfirst[(size_t)k], kfirst[(size_t)k + 1]);
+  std::vector<int64_t> order;
+  for (int pass = 1; pass >= 0; --pass)
+    for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
+  std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
+  std::vector<int32_t> items;
+  items.reserve(byk.size());
+  for (size_t x = 0; x < order.size(); ++x) {
+    const size_t k = (size_t)order[x];
+    items.insert(items.end(), byk.begin() + 4 * kfirst[k], byk.begin() + 4 * kfirst[k + 1]);
+    if ((int64_t)x + 1 == D.nII_total) D.symm_nitems[0] = (int64_t)items.size() / 4;
+  }
+  D.symm_nitems[1] = (int64_t)items.size() / 4;
+  int rc = 0;
+  if ((rc = dev_upload(&D.symm_pos, pos, D.bytes))) return rc;
+  if ((rc = dev_upload(&D.symm_heavy, heavy, D.bytes))) return rc;
+  D.symm_nheavy = (int64_t)heavy.size();
+  if ((rc = dev_upload(&D.symm_items, items, D.bytes))) return rc;
+  return dev_upload(&D.symm_tptr, tptr, D.bytes);
+}
+
+int csp_symm(csp_ctx* c, const double* X, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t nrhs, double alpha, double beta,
+             void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int mm = sw_int("SMCP_SYMM_MM", 1);       // read on every call: tools/symm_time.py alternates the settings in one process
+  DeviceCtx& D = c->D;
+  const Symbolic& S = c->S;
+  // (grid limits of the column-block dimension; a partitioned context holds valid panels on its own cliques only)
+  if (nrhs < 1 || nrhs > ((int64_t)1 << 18) || ldb < S.n || ldc < S.n || c->xr_world > 1) return SMCP_EINVAL;
+  {
+    const uintptr_t b0 = (uintptr_t)B, b1 = (uintptr_t)(B + ldb * (nrhs - 1) + S.n);
+    const uintptr_t c0 = (uintptr_t)C, c1 = (uintptr_t)(C + ldc * (nrhs - 1) + S.n);
+    if (c0 < b1 && b0 < c1) return SMCP_EINVAL;   // phase 2 would write what phase 1 of a later column block still reads
+  }
+  if (int rc = symm_setup(c)) return rc;
+  if (D.symm_ntot * nrhs > D.max_rhs * D.tmplen) return SMCP_ENOMEM;
+  hipStream_t st = (hipStream_t)stream;
+  // tile products for the large fronts from eight columns on and for every front from SYMM_MM_ALL columns on (the gates of
+  // csp_trmm); everything else, and everything on the generic / deterministic route, on the FMA kernel
+  const bool mm_ok = mm && !use_generic(c) && use_large();
+  const bool tiles_all = mm_ok && mm != 2 && nrhs >= SYMM_MM_ALL;
+  const bool tiles = tiles_all || (mm_ok && (nrhs >= 8 || mm == 2) && D.symm_nitems[0] > 0);
+  SymmArgs a;
+  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.symm_items; a.pos = D.symm_pos;
+  a.X = X; a.B = B; a.U = D.tmp; a.ntot = D.symm_ntot; a.nrhs = (int)nrhs; a.ldb = ldb;
+  if (alpha != 0.0) {                             // alpha == 0: neither X nor B is read
+    a.item0 = tiles_all ? 0 : tiles ? (int)D.symm_nitems[0] : 0;
+    a.nitems = tiles_all ? 0 : (int)D.symm_nitems[1] - a.item0;
+    auto fma = [&](auto cb) {      // CB columns of B per wave: X is read once per block of CB columns
+      constexpr int CB = decltype(cb)::value;
+      const dim3 grid((unsigned)((a.nitems + SYMM_WAVES - 1) / SYMM_WAVES), (unsigned)((a.nrhs + CB - 1) / CB));
+      launch(c, KID_symm_fma, k_symm_fma<CB>, grid, dim3(64 * SYMM_WAVES), st, a);
+    };
+    if (a.nitems) {
+      if (nrhs == 1) fma(std::integral_constant<int, 1>{});
+      else if (nrhs <= 4) fma(std::integral_constant<int, 4>{});
+      else fma(std::integral_constant<int, 8>{});
+    }
+    if (tiles) {
+      a.item0 = 0;
+      a.nitems = (int)D.symm_nitems[tiles_all ? 1 : 0];
+      launch(c, KID_symm_mm, k_symm_mm, dim3((unsigned)a.nitems, (unsigned)tiles64((int)nrhs)), dim3(256), st, a);
+    }
+  }
+  {
+    const int64_t cap = 16 * (int64_t)D.ncu;
+    const int light = (int)std::min<int64_t>((S.n * nrhs + 255) / 256, cap);
+    const int64_t nheavy = alpha != 0.0 ? D.symm_nheavy : 0;
+    const int hw = (int)std::min<int64_t>((nheavy * nrhs + 3) / 4, cap);
+    launch(c, KID_symm_combine, k_symm_combine, dim3((unsigned)(light + hw)), dim3(256), st, (const int64_t*)D.symm_tptr,
+           (const int32_t*)D.symm_heavy, (int)nheavy, light, (const double*)D.tmp, a.ntot, C, S.n, (int)nrhs, ldc, alpha, beta);
   }
   HIPCHK(end_call(c));
   return 0;

@@ -180,6 +180,14 @@ struct DeviceCtx {
   int32_t* syr2k_items = nullptr; int64_t syr2k_nitems[2] = {0, 0};
   int32_t* syr2k_tiles = nullptr; int64_t syr2k_ntiles[2] = {0, 0};
   bool syr2k_ready = false;
+  // products of the matrix itself (front_symm.hip): the contribution index (row i of C owns the positions [symm_tptr[i],
+  // symm_tptr[i + 1]) of the list of all symm_ntot partials; symm_pos: per item the positions of its row partials, then of its
+  // column partials), the rows with more than SYMM_HEAVY partials, and the (clique, row chunk, column part, base in symm_pos)
+  // items, those of the large fronts FIRST ([0]: theirs, [1]: all).  symm_ntot: -1 until counted (csp_symm_positions: host only)
+  int64_t* symm_tptr = nullptr; int32_t* symm_pos = nullptr;
+  int32_t* symm_heavy = nullptr; int64_t symm_nheavy = 0;
+  int32_t* symm_items = nullptr; int64_t symm_nitems[2] = {0, 0};
+  int64_t symm_ntot = -1;
   int64_t bytes = 0;
 };
 
