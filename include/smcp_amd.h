@@ -276,8 +276,35 @@ int dense_potrs(csp_ctx* ctx, const double* A, int64_t n, int64_t lda, double* B
  * and by (length m) with y for  [-kk*W^-1  A^adj; A 0][x;y] = [bx;by]. */
 int kkt_solve(csp_ctx* ctx, const double* L, const double* Y, const double* H, int64_t ldh,
               double kk, double* bx, double* by, void* stream);
+/* The same solve for a BLOCK of nrhs right-hand sides on one factorisation (solvers.py:506-541, the dense solve at 526): row r of
+ * BX is a blkval at BX + r * ldbx, row r of BY a vector of length m at BY + r * ldby; every pair is overwritten with the
+ * (x, y) kkt_solve computes for it, with the same kk for all rows.  Every stage is one launch sequence for the rows of a
+ * chunk: the number of launches does not depend on nrhs within a chunk.  Entries of a row beyond blklen / m are never
+ * written; L, Y and H are only read.  A row's result does not depend on what the other rows hold.
+ * WORKSPACE.  The W(bx) of a chunk of c rows live in c rows of the constraint stack and the c x m temporaries behind
+ * them: c + ceil(c m / blklen) <= max_rhs (csp_device_init).  A larger nrhs is processed in chunks of the largest such c
+ * (kkt_solve_many_chunk), so any nrhs works on the workspace the context has; SMCP_ENOMEM when max_rhs < 2 or no c fits.
+ * SMCP_EINVAL: nrhs < 1; ldh < m; ldbx < blklen or ldby < m with nrhs > 1; no constraints installed; BX, BY and H
+ * overlapping one another by address range (nothing is written); a context under a subtree partition over more than one
+ * rank (csp_set_partition: the sharded solve_ has no block form).
+ * A Schur complement whose factorisation waits under csp_lazy_status is factored first, on `stream`, where it stands (no
+ * side stream).  The Q factor of kkt_qr_factor is dropped as by kkt_solve, and a failure of chol(Y_AA) is reported or
+ * latched as by kkt_solve.  Does not synchronise. */
+int kkt_solve_many(csp_ctx* ctx, const double* L, const double* Y, const double* H, int64_t ldh, double kk, double* BX,
+                   int64_t ldbx, double* BY, int64_t ldby, int64_t nrhs, void* stream);
+/* The chunk rule of kkt_solve_many: the largest c with c + ceil(c m / blklen) <= max_rhs, 0 when max_rhs < 2 or none fits.
+ * Host only: needs neither a context nor a device. */
+int64_t kkt_solve_many_chunk(int64_t m, int64_t blklen, int64_t max_rhs);
+/* L L^T Z = B for a block of nrhs columns (column r at B + r * ldb, ldb >= n) with a lower Cholesky factor A from anywhere
+ * (dense_potrf, or uploaded: only the lower triangle is read).  n <= 128: one launch with the factor in LDS; beyond,
+ * 2 ceil(n / 64) block steps spread over the chip, whatever nrhs is; the factor is read once per triangle and block of 32
+ * columns.  The diagonal blocks are solved by substitution (no explicit inverse is formed or used, cached or not).  A, the
+ * rows of A beyond n and the entries B[r * ldb + n ...] are not written; a column's result does not depend on the other
+ * columns; the order of every sum is fixed.  SMCP_EINVAL: n < 1, lda < n, nrhs < 1, ldb < n with nrhs > 1, B overlapping
+ * A.  Does not synchronise.  What kkt_solve_many calls; dense_potrs keeps its own routes. */
+int dense_potrs_many(csp_ctx* ctx, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, void* stream);
 
-/* kkt_qr (solvers.py:413-475 feas, 1843-1905 esd): the QR-based KKT solver.  kkt_qr_factor builds the stack of
+/* kkt_qr(solvers.py:413-475 feas, 1843-1905 esd): the QR-based KKT solver.  kkt_qr_factor builds the stack of
  * half-Hessian images of ALL m constraints (call kkt_set_tnzcols(ctx, 0) before kkt_set_constraints: the reference
  * does not split off column-sparse constraints on this path, solvers.py:242,551-556) and factors it, At = Q R, by
  * Cholesky-QR iterations on the device (csrc/kkt_qr.hip; a shifted first pass when chol(At^T At) breaks down).  Q

@@ -73,6 +73,7 @@ enum {
   KID_psd_zero, KID_psd_scatter, KID_psd_solve, KID_psd_fill, KID_top_chol, KID_lf_trtri,
   KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine, KID_syr2k_fma, KID_syr2k_mm,
   KID_symm_fma, KID_symm_mm, KID_symm_combine,
+  KID_potrs_many_small, KID_potrs_many_step, KID_aadj_sub_many, KID_kkt_many_y, KID_kkt_many_scale,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -95,7 +96,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_edm_rank", "k_edm_reduce", "k_edm_factor", "k_edm_dense", "k_hess_down_fam", "k_hess_up_fam1",
   "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri",
   "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm",
-  "k_symm_fma", "k_symm_mm", "k_symm_combine"};
+  "k_symm_fma", "k_symm_mm", "k_symm_combine",
+  "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -4218,4 +4220,5 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 }  // extern "C"
 
 #include "kkt.hip"
+#include "kkt_many.hip"
 #include "kkt_qr.hip"

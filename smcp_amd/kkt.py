@@ -24,6 +24,19 @@ def _empty(n, dev):
     return t
 
 
+def solve_many_chunks(nrhs, m, blklen, max_rhs):
+    """The chunks KKTSystem.solve_many processes nrhs right-hand sides in: c right-hand sides need c rows of the
+    constraint stack for W(bx) and c * m doubles behind them, c + ceil(c * m / blklen) <= max_rhs; every chunk but the
+    last is the largest such c (the rule of kkt_solve_many itself: include/smcp_amd.h kkt_solve_many_chunk; host only)."""
+    if nrhs < 1:
+        raise ValueError("nrhs must be at least 1")
+    c = int(_lib.lib().kkt_solve_many_chunk(int(m), int(blklen), int(max_rhs)))
+    if c < 1:
+        raise MemoryError("max_rhs = %d rows of %d doubles do not hold one right-hand side and its %d temporaries"
+                          % (max_rhs, blklen, m))
+    return [c] * (nrhs // c) + ([nrhs % c] if nrhs % c else [])
+
+
 def column_range(m, rank, world):
     """Contiguous block of Schur-complement columns owned by `rank` (balanced to within one column)."""
     return (m * rank) // world, (m * (rank + 1)) // world
@@ -726,6 +739,28 @@ class KKTSystem(ShardedSchur):
             return bx, by
 
         return solve_
+
+    def solve_many(self, L, Y, BX, BY, kk):
+        """The solve_ of kkt_chol (solvers.py:506-541) for a block of right-hand sides on ONE factorisation: valid after
+        factor(L, Y) of this system.  BX: float64 device tensor (k, >= blklen) with stride(1) == 1, row r a blkval (the
+        batched form chordal.hessian accepts); BY: (k, >= m).  Every pair of rows is overwritten with its (x, y), the same
+        kk for all; entries beyond blklen / m stay.  Any k works on the workspace the system has: rows are processed in
+        chunks (solve_many_chunks).  Returns (BX, BY).  Not sharded (include/smcp_amd.h: kkt_solve_many)."""
+        if self._sharded_pair(L, Y):
+            raise NotImplementedError("solve_many has no sharded form: use the solve_ closure of factor(L, Y, group)")
+        bl, m = self.symb.blklen, self.m
+        for T, width, what in ((BX, bl, "BX"), (BY, m, "BY")):
+            if not (torch.is_tensor(T) and T.dtype == torch.float64 and T.is_cuda and T.dim() == 2 and T.shape[0] >= 1
+                    and T.shape[1] >= width and T.stride(1) == 1 and (T.shape[0] == 1 or T.stride(0) >= width)):
+                raise ValueError("%s must be a float64 device tensor (k, >= %d) with unit stride along a row" % (what, width))
+        if BX.shape[0] != BY.shape[0]:
+            raise ValueError("BX and BY must have the same number of rows")
+        self._own()
+        sync_cache(self.symb, L, Y)
+        _chk(_lib.lib().kkt_solve_many(self.symb.handle, L.blkval.data_ptr(), Y.blkval.data_ptr(), self.H.data_ptr(), self.m,
+                                       float(kk), BX.data_ptr(), BX.stride(0), BY.data_ptr(), BY.stride(0), BX.shape[0],
+                                       _stream()), "kkt_solve_many")
+        return BX, BY
 
     def factor_qr(self, L, Y, group=None):
         """kkt_qr(L, Y) (solvers.py:413-475): QR factorisation of the stack of half-Hessian images of the
