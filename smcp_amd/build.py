@@ -12,8 +12,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsmcp_amd.so")
 SOURCES = ["capi.hip", "symbolic.cpp"]
-DEPS = ["front_large.hip", "front_top.hip", "front_mfma.hip", "capi.hip", "kkt.hip", "kkt_many.hip", "kkt_qr.hip", "front_generic.hip", "front_mrc.hip", "front_edm.hip", "front_psd.hip", "front_trmm.hip", "front_syr2k.hip", "front_symm.hip", "front_downfam.hip", "front_upfam.hip", "wgblas.hpp", "context.hpp", "symbolic.cpp",
-        "symbolic.hpp", "../../include/smcp_amd.h"]
 
 
 def _stale():

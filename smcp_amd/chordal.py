@@ -226,15 +226,21 @@ def hessian(L, Y, U, adj=False, inv=False):
                                  symb.blklen, a, i, _stream()), "hessian")
 
 
+def _fit_workspace(symb, positions, k):
+    """Grows max_rhs so that `positions` partial results for each of k columns fit the workspace (the library returns
+    SMCP_ENOMEM otherwise)."""
+    need = -(-positions * k // max(1, 2 * symb.blklen))
+    if symb._max_rhs < need:
+        symb.device_init(symb._device, need)
+
+
 def trsm(L, B, trans="N"):
     """B: (n x k) column-major dense right-hand side given as a torch tensor of shape (k, n)
     (row r of the tensor = column r of B), rows in the PERMUTED order."""
     symb = L.symb
     _ensure(symb)
     assert B.dim() == 2 and B.stride(1) == 1 and B.shape[1] == symb.n
-    need = -(-int(symb.sepptr[-1]) * B.shape[0] // max(1, 2 * symb.blklen))
-    if symb._max_rhs < need:
-        symb.device_init(symb._device, need)
+    _fit_workspace(symb, int(symb.sepptr[-1]), B.shape[0])
     _chk(_lib.lib().csp_trsm(symb.handle, L.blkval.data_ptr(), B.data_ptr(), B.shape[0], B.stride(0),
                              1 if trans in ("T", 1, True) else 0, _stream()), "trsm")
 
@@ -248,9 +254,7 @@ def trmm(L, B, alpha=1.0, trans="N"):
     symb = L.symb
     _ensure(symb)
     assert B.dim() == 2 and B.stride(1) == 1 and B.shape[1] == symb.n
-    need = -(-int(symb.sepptr[-1]) * B.shape[0] // max(1, 2 * symb.blklen))
-    if symb._max_rhs < need:
-        symb.device_init(symb._device, need)
+    _fit_workspace(symb, int(symb.sepptr[-1]), B.shape[0])
     _chk(_lib.lib().csp_trmm(symb.handle, L.blkval.data_ptr(), B.data_ptr(), B.shape[0], B.stride(0), float(alpha),
                              1 if trans in ("T", 1, True) else 0, _stream()), "trmm")
 
@@ -268,31 +272,27 @@ def syr2k(X, U, V, alpha=1.0, beta=1.0):
     row r is column r of the block, rows in the PERMUTED order.  They are not written; V may be U.  Every slot of X.blkval is
     written (those outside the pattern as exactly 0.0), X is not read when beta == 0, U and V are not read when alpha == 0,
     and the same arguments give the same bits from call to call.  One or two launches whatever the tree (csp_syr2k)."""
-    symb = X.symb
-    ldu = _dense_block(symb, U, "U")
-    ldv = _dense_block(symb, V, "V")
-    assert U.shape[0] == V.shape[0]
-    assert U.is_cuda and V.is_cuda
-    _ensure(symb)
-    X.touched()
-    try:
-        _chk(_lib.lib().csp_syr2k(symb.handle, X.blkval.data_ptr(), U.data_ptr(), V.data_ptr(), U.shape[0], ldu, ldv,
-                                  float(alpha), float(beta), _stream()), "syr2k")
-    finally:
-        note_cache(symb, X)
+    _rank_update(X, U, V, alpha, beta, "syr2k")
 
 
 def syrk(X, U, alpha=1.0, beta=1.0):
     """X <- beta X + alpha P_V(U U^T), in place, for U as in ``syr2k``: P_V(Y Y^T) of a low-rank factor (the Y of
     ``mrcompletion`` as ``Y.t().contiguous()``) without an n x n intermediate."""
+    _rank_update(X, U, None, alpha, beta, "syrk")
+
+
+def _rank_update(X, U, V, alpha, beta, name):
+    """csp_syr2k; V None: the rank-k form (V absent)."""
     symb = X.symb
     ldu = _dense_block(symb, U, "U")
-    assert U.is_cuda
+    ldv = 0 if V is None else _dense_block(symb, V, "V")
+    assert V is None or U.shape[0] == V.shape[0]
+    assert U.is_cuda and (V is None or V.is_cuda)
     _ensure(symb)
     X.touched()
     try:
-        _chk(_lib.lib().csp_syr2k(symb.handle, X.blkval.data_ptr(), U.data_ptr(), None, U.shape[0], ldu, 0,
-                                  float(alpha), float(beta), _stream()), "syrk")
+        _chk(_lib.lib().csp_syr2k(symb.handle, X.blkval.data_ptr(), U.data_ptr(), None if V is None else V.data_ptr(),
+                                  U.shape[0], ldu, ldv, float(alpha), float(beta), _stream()), name)
     finally:
         note_cache(symb, X)
 
@@ -322,9 +322,7 @@ def symm(X, B, C=None, alpha=1.0, beta=0.0):
     assert C.is_cuda and C.shape[0] == B.shape[0]
     _ensure(symb)
     lib = _lib.lib()
-    need = -(-int(lib.csp_symm_positions(symb.handle)) * B.shape[0] // max(1, 2 * symb.blklen))
-    if symb._max_rhs < need:
-        symb.device_init(symb._device, need)
+    _fit_workspace(symb, int(lib.csp_symm_positions(symb.handle)), B.shape[0])
     _chk(lib.csp_symm(symb.handle, X.blkval.data_ptr(), B.data_ptr(), ldb, C.data_ptr(), ldc, B.shape[0], float(alpha),
                       float(beta), _stream()), "symm")
     return C

@@ -318,6 +318,17 @@ int dev_alloc(T** dst, int64_t count, int64_t& bytes) {
   return 0;
 }
 
+// Grows a scratch buffer that no call keeps to at least `need` elements; its contents are lost.  An older buffer is freed
+// only once the stream has drained: launches of earlier calls may still use it.
+template <class T>
+int dev_grow(T** buf, int64_t* len, int64_t need, int64_t& bytes, hipStream_t st) {
+  if (*len >= need) return 0;
+  if (*buf) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*buf)); bytes -= *len * (int64_t)sizeof(T); *buf = nullptr; *len = 0; }
+  if (int rc = dev_alloc(buf, need, bytes)) return rc;
+  *len = need;
+  return 0;
+}
+
 TreeArgs tree_args(csp_ctx* c) {
   TreeArgs a;
   a.cl = c->D.cl;
@@ -2293,15 +2304,13 @@ void csp_symbolic_destroy(csp_ctx* c) {
     hipSetDevice(D.device);
     void* ptrs[] = {D.lfsp_skip, D.famt_skip, D.both_skip, D.trsm_x, D.fp, D.fp_bad, D.gsl_start, D.gsl_len, D.lg_list, D.lg_slot, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.sp_rt, D.sp_mk, D.lfsp_list, D.faci, D.lfd, D.lev3idx, D.updp, D.gp_tptr, D.gp_tgt, D.gp_cptr, D.gp_src, D.sw, D.gpart, D.lev2idx, D.lk, D.cl, D.rowidx, D.relidx, D.chidx, D.levidx, D.upd, D.yaa, D.fac, D.tmp, D.tmpptr,
                     D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
-                    D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner,
-                    D.mrc_ws, D.mrc_int, D.mrc_xdiag, D.mrc_list, D.psd_tasks, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra,
-                    D.trmm_tptr, D.trmm_pos, D.trmm_heavy, D.trmm_items[0], D.trmm_items[1], D.trmm_tiles[0], D.trmm_tiles[1],
-                    D.syr2k_items, D.syr2k_tiles, D.symm_tptr, D.symm_pos, D.symm_heavy, D.symm_items};
+                    D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner};
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
     D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
     for (auto& kv : c->flow_plans) { if (kv.second.own_ptr) hipFree(kv.second.own_ptr); if (kv.second.own_tile) hipFree(kv.second.own_tile); }
     for (void* p : ptrs) if (p) hipFree(p);
+    D.mrc.release(); D.psd.release(); D.trmm.release(); D.syr2k.release(); D.symm.release();
     for (auto& G : c->lfsp_grp) { if (G.ptr) hipFree(G.ptr); if (G.list) hipFree(G.list); }
     for (auto& G : c->famt_grp) { if (G.ptr) hipFree(G.ptr); if (G.list) hipFree(G.list); }
     for (int q = 0; q < 2; ++q) {
@@ -3153,13 +3162,8 @@ int trsm_impl(csp_ctx* c, const double* L, const double* Y, double* B, int64_t n
     // tile products with the inverse-form factor (front_large.hip: k_trsm_mm_*): the generic kernels below solve every
     // clique's triangle by substitution in one workgroup per sixteen columns -- 0.48 ms per level on config 4
     if (int rc = prep_lk_cached(c, L, Y, st)) return rc;
-    const int64_t need = ldb * nrhs;
     DeviceCtx& D = c->D;
-    if (D.trsm_x_len < need) {
-      if (D.trsm_x) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(D.trsm_x)); D.bytes -= D.trsm_x_len * 8; D.trsm_x = nullptr; D.trsm_x_len = 0; }
-      if (int rc = dev_alloc(&D.trsm_x, need, D.bytes)) return rc;
-      D.trsm_x_len = need;
-    }
+    if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, ldb * nrhs, D.bytes, st)) return rc;
     MfmaArgs a0 = mfma_args(c, nullptr, 0, (int)nrhs);
     const unsigned ct = (unsigned)tiles64((int)nrhs);
     auto level = [&](int64_t l) {
@@ -3200,730 +3204,12 @@ int csp_trsm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, 
   return trsm_impl(c, L, nullptr, B, nrhs, ldb, trans, (hipStream_t)stream);
 }
 
-// ---- products with the factor (front_trmm.hip) ----------------------------------------------------------------------
-// Once per context: the transposed separator index (specified by the numpy restatement of tests/trmm_ref.py: position p
-// of its lists (tk, tq) is pos[sepptr[tk[p]] + tq[p]] here), the item lists of the FMA kernels and the row tiles of the
-// tile products.
-static int trmm_setup(csp_ctx* c) {
-  DeviceCtx& D = c->D;
-  if (D.trmm_tptr) return 0;
-  const Symbolic& S = c->S;
-  if (S.sepptr[S.nsn] >= ((int64_t)1 << 31)) return SMCP_EINVAL;      // positions are 32-bit
-  std::vector<int64_t> tptr((size_t)S.n + 1, 0);
-  for (int64_t k = 0; k < S.nsn; ++k)
-    for (int64_t q = 0; q < S.na(k); ++q) ++tptr[(size_t)S.rowidx[S.rowptr[k] + S.nn(k) + q] + 1];
-  for (int64_t i = 0; i < S.n; ++i) tptr[(size_t)i + 1] += tptr[(size_t)i];
-  std::vector<int32_t> pos((size_t)S.sepptr[S.nsn]);
-  {
-    std::vector<int64_t> fill(tptr.begin(), tptr.end() - 1);
-    for (int64_t k = 0; k < S.nsn; ++k)           // ascending k: the order of the sums of k_trmm_combine
-      for (int64_t q = 0; q < S.na(k); ++q) pos[(size_t)(S.sepptr[k] + q)] = (int32_t)fill[(size_t)S.rowidx[S.rowptr[k] + S.nn(k) + q]]++;
-  }
-  std::vector<int32_t> heavy;
-  for (int64_t i = 0; i < S.n; ++i) if (tptr[(size_t)i + 1] - tptr[(size_t)i] > TRMM_HEAVY) heavy.push_back((int32_t)i);
-  // items: the cliques outside the large class, then the large fronts; for N every group is padded to whole workgroups
-  // (clique -1) and the row chunks of wide supernodes come last, four items (the parts of the k range) each
-  std::vector<int32_t> items[2];
-  int64_t nsmall[2] = {0, 0};
-  auto pad = [&]() { while ((items[0].size() / 2) % TRMM_WAVES) { items[0].push_back(-1); items[0].push_back(0); } };
-  for (int pass = 0; pass < 3; ++pass) {          // N: small, large, split
-    for (int64_t k = 0; k < S.nsn; ++k) {
-      const bool large = c->large_mask[(size_t)k] != 0, split = large && S.nn(k) >= TRMM_SPLIT_NN;
-      if (pass != (split ? 2 : large ? 1 : 0)) continue;
-      for (int64_t ch = 0; ch < (S.nf(k) + 63) / 64; ++ch)
-        for (int part = 0; part < (split ? TRMM_WAVES : 1); ++part) { items[0].push_back((int32_t)k); items[0].push_back(trmm_code((int)ch, part, split ? 1 : 0)); }
-    }
-    pad();
-    if (pass == 0) nsmall[0] = (int64_t)items[0].size() / 2;
-  }
-  for (int pass = 0; pass < 2; ++pass) {          // T: small, large
-    for (int64_t k = 0; k < S.nsn; ++k) {
-      if ((c->large_mask[(size_t)k] != 0) != (pass == 1)) continue;
-      for (int64_t ch = 0; ch < (S.nn(k) + TRMM_JC - 1) / TRMM_JC; ++ch) { items[1].push_back((int32_t)k); items[1].push_back((int32_t)ch); }
-    }
-    if (pass == 0) nsmall[1] = (int64_t)items[1].size() / 2;
-  }
-  // row tiles of the tile products: the large fronts first (the long tiles start first), widest front first among them
-  std::vector<int32_t> tiles[2];
-  int64_t nlarge[2] = {0, 0};
-  {
-    std::vector<int64_t> order;
-    for (int pass = 1; pass >= 0; --pass)
-      for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
-    std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
-    for (size_t x = 0; x < order.size(); ++x) {
-      const int64_t k = order[x];
-      for (int t = 0; t < 2; ++t) {
-        for (int64_t rt = 0; rt < tiles64((int)(t ? S.nn(k) : S.nf(k))); ++rt) { tiles[t].push_back((int32_t)k); tiles[t].push_back((int32_t)rt); }
-        if ((int64_t)x + 1 == D.nII_total) nlarge[t] = (int64_t)tiles[t].size() / 2;
-      }
-    }
-  }
-  int rc = 0;
-  if ((rc = dev_upload(&D.trmm_pos, pos, D.bytes))) return rc;
-  for (int t = 0; t < 2; ++t) {
-    if ((rc = dev_upload(&D.trmm_tiles[t], tiles[t], D.bytes))) return rc;
-    D.trmm_ntiles[t][0] = nlarge[t];
-    D.trmm_ntiles[t][1] = (int64_t)tiles[t].size() / 2;
-  }
-  if ((rc = dev_upload(&D.trmm_heavy, heavy, D.bytes))) return rc;
-  D.trmm_nheavy = (int64_t)heavy.size();
-  for (int t = 0; t < 2; ++t) {
-    if ((rc = dev_upload(&D.trmm_items[t], items[t], D.bytes))) return rc;
-    D.trmm_nitems[t][0] = nsmall[t];
-    D.trmm_nitems[t][1] = (int64_t)items[t].size() / 2;
-  }
-  return dev_upload(&D.trmm_tptr, tptr, D.bytes);
-}
+}  // extern "C"
 
-int trmm_impl(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans, hipStream_t st) {
-  static const int mm = sw_int("SMCP_TRMM_MM", 1);
-  DeviceCtx& D = c->D;
-  const Symbolic& S = c->S;
-  if (int rc = trmm_setup(c)) return rc;
-  if (!trans && S.sepptr[S.nsn] * nrhs > D.max_rhs * D.tmplen) return SMCP_ENOMEM;
-  const int64_t need = ldb * nrhs;
-  if (D.trsm_x_len < need) {      // the scratch image of B is csp_trsm's: neither call keeps it
-    if (D.trsm_x) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(D.trsm_x)); D.bytes -= D.trsm_x_len * 8; D.trsm_x = nullptr; D.trsm_x_len = 0; }
-    if (int rc = dev_alloc(&D.trsm_x, need, D.bytes)) return rc;
-    D.trsm_x_len = need;
-  }
-  // tile products for the large fronts from eight columns on (the gate of csp_trsm) and for every front from TRMM_MM_ALL
-  // columns on; everything else, and everything on the generic / deterministic route, on the FMA kernels
-  const bool mm_ok = mm && !use_generic(c) && use_large();
-  const bool tiles_all = mm_ok && mm != 2 && nrhs >= TRMM_MM_ALL;
-  const bool tiles = tiles_all || (mm_ok && nrhs >= 8 && D.nII_total > 0);
-  TrmmArgs a;
-  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.trmm_items[trans];
-  a.nitems = tiles_all ? 0 : (int)D.trmm_nitems[trans][tiles ? 0 : 1];
-  a.tiles = D.trmm_tiles[trans];
-  a.L = L; a.B = B; a.X = D.trsm_x; a.U = D.tmp; a.pos = D.trmm_pos; a.ntot = S.sepptr[S.nsn]; a.nrhs = (int)nrhs; a.ldb = ldb;
-  auto fma = [&](auto cb) {        // CB columns of B per wave: L is read once per block of CB columns
-    constexpr int CB = decltype(cb)::value;
-    const dim3 grid((unsigned)((a.nitems + TRMM_WAVES - 1) / TRMM_WAVES), (unsigned)((a.nrhs + CB - 1) / CB));
-    if (!trans) launch(c, KID_trmm_n, k_trmm_n<CB>, grid, dim3(64 * TRMM_WAVES), st, a);
-    else launch(c, KID_trmm_t, k_trmm_t<CB>, grid, dim3(64 * TRMM_WAVES), st, a);
-  };
-  if (a.nitems) {
-    if (nrhs == 1) fma(std::integral_constant<int, 1>{});
-    else if (nrhs <= 4) fma(std::integral_constant<int, 4>{});
-    else fma(std::integral_constant<int, 8>{});
-  }
-  if (tiles) {
-    const dim3 grid((unsigned)D.trmm_ntiles[trans][tiles_all ? 1 : 0], (unsigned)tiles64((int)nrhs));
-    if (!trans) launch(c, KID_trmm_mm, k_trmm_mm<false>, grid, dim3(256), st, a);
-    else launch(c, KID_trmm_mm, k_trmm_mm<true>, grid, dim3(256), st, a);
-  }
-  {
-    const int64_t cap = 16 * (int64_t)D.ncu;
-    const int light = (int)std::min<int64_t>((S.n * nrhs + 255) / 256, cap);
-    const int64_t nheavy = trans ? 0 : D.trmm_nheavy;
-    const int hw = (int)std::min<int64_t>((nheavy * nrhs + 3) / 4, cap);
-    launch(c, KID_trmm_combine, k_trmm_combine, dim3((unsigned)(light + hw)), dim3(256), st, (const int64_t*)(trans ? nullptr : D.trmm_tptr),
-           (const int32_t*)D.trmm_heavy, (int)nheavy, light, (const double*)D.trsm_x, (const double*)D.tmp, a.ntot, B, S.n, (int)nrhs, ldb, alpha);
-  }
-  HIPCHK(end_call(c));
-  return 0;
-}
-int csp_trmm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, double alpha, int trans, void* stream) {
-  if (int rc = ready(c)) return rc;
-  // (grid limits of the column-block dimension; a partitioned context holds valid factors on its own cliques only)
-  if (nrhs < 1 || nrhs > ((int64_t)1 << 18) || ldb < c->S.n || c->xr_world > 1) return SMCP_EINVAL;
-  return trmm_impl(c, L, B, nrhs, ldb, alpha, trans ? 1 : 0, (hipStream_t)stream);
-}
+#include "products.hip"
+#include "completions.hip"
 
-// ---- rank-k updates projected on the pattern (front_syr2k.hip) ------------------------------------------------------
-// Once per context: the item list of the FMA kernel and the tile list of the tile products.
-static int syr2k_setup(csp_ctx* c) {
-  DeviceCtx& D = c->D;
-  if (D.syr2k_ready) return 0;
-  const Symbolic& S = c->S;
-  std::vector<int32_t> items, tiles;
-  auto list = [&](std::vector<int32_t>& out, int64_t k, int rows, int cols) {       // computing entries, then the zero-only ones
-    const int64_t nf = S.nf(k), nn = S.nn(k);
-    for (int zero = 0; zero < 2; ++zero)
-      for (int64_t r = 0; r < (nf + rows - 1) / rows; ++r)
-        for (int64_t j = 0; j < (nn + cols - 1) / cols; ++j) {
-          const bool above = std::min<int64_t>(r * rows + rows, nf) - 1 < j * cols;   // the last row lies above the first column
-          if (above == (zero == 1)) { out.push_back((int32_t)k); out.push_back((int32_t)r); out.push_back((int32_t)j); out.push_back(zero); }
-        }
-  };
-  for (int pass = 0; pass < 2; ++pass) {          // items: small, large
-    for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) list(items, k, 64, SYR2K_JC);
-    D.syr2k_nitems[pass] = (int64_t)items.size() / 4;
-  }
-  {                                               // tiles: large (widest front first: the long tiles start first), small
-    std::vector<int64_t> order;
-    for (int pass = 1; pass >= 0; --pass)
-      for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
-    std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
-    for (size_t x = 0; x < order.size(); ++x) {
-      list(tiles, order[x], LT, LT);
-      if ((int64_t)x + 1 == D.nII_total) D.syr2k_ntiles[0] = (int64_t)tiles.size() / 4;
-    }
-    D.syr2k_ntiles[1] = (int64_t)tiles.size() / 4;
-  }
-  if (D.syr2k_nitems[1] >= ((int64_t)1 << 31) || D.syr2k_ntiles[1] >= ((int64_t)1 << 31)) return SMCP_EINVAL;     // grid dimension
-  if (int rc = dev_upload(&D.syr2k_items, items, D.bytes)) return rc;
-  if (int rc = dev_upload(&D.syr2k_tiles, tiles, D.bytes)) return rc;
-  D.syr2k_ready = true;
-  return 0;
-}
-
-int csp_syr2k(csp_ctx* c, double* X, const double* U, const double* V, int64_t k, int64_t ldu, int64_t ldv, double alpha, double beta,
-              void* stream) {
-  if (int rc = ready(c)) return rc;
-  const int mm = sw_int("SMCP_SYR2K_MM", 1);      // read on every call: tools/syr2k_time.py alternates the settings in one process
-  // (the inner dimension 2k is an int; a partitioned context keeps valid panels on its own cliques only)
-  if (k < 1 || k > ((int64_t)1 << 18) || ldu < c->S.n || (V && ldv < c->S.n) || c->xr_world > 1) return SMCP_EINVAL;
-  if (int rc = syr2k_setup(c)) return rc;
-  DeviceCtx& D = c->D;
-  hipStream_t st = (hipStream_t)stream;
-  invalidate_tags(c, X);
-  // tile products for the large fronts from SYR2K_MM_LARGE ranks on and for every front from SYR2K_MM_ALL ranks on; everything
-  // else, and everything on the generic / deterministic route, on the FMA kernel
-  const bool mm_ok = mm && !use_generic(c) && use_large();
-  const bool tiles_all = mm_ok && mm != 2 && k >= SYR2K_MM_ALL;
-  const bool tiles = tiles_all || (mm_ok && k >= SYR2K_MM_LARGE && D.nII_total > 0);
-  Syr2kArgs a;
-  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.syr2k_items; a.tiles = D.syr2k_tiles;
-  a.nitems = tiles_all ? 0 : (int)D.syr2k_nitems[tiles ? 0 : 1];
-  a.X = X; a.U = U; a.V = V; a.k = (int)k; a.ldu = ldu; a.ldv = V ? ldv : ldu; a.alpha = alpha; a.beta = beta;
-  auto fma_launch = [&](auto rb) {
-    constexpr int RB = decltype(rb)::value;
-    const dim3 grid((unsigned)((a.nitems + SYR2K_WAVES - 1) / SYR2K_WAVES));
-    if (V) launch(c, KID_syr2k_fma, k_syr2k_fma<RB, true>, grid, dim3(64 * SYR2K_WAVES), st, a);
-    else launch(c, KID_syr2k_fma, k_syr2k_fma<RB, false>, grid, dim3(64 * SYR2K_WAVES), st, a);
-  };
-  if (a.nitems) {
-    if (k == 1) fma_launch(std::integral_constant<int, 1>{});
-    else if (k <= 4) fma_launch(std::integral_constant<int, 4>{});
-    else fma_launch(std::integral_constant<int, 8>{});
-  }
-  const int64_t ntiles = tiles ? D.syr2k_ntiles[tiles_all ? 1 : 0] : 0;
-  if (ntiles) {
-    if (V) launch(c, KID_syr2k_mm, k_syr2k_mm<true>, dim3((unsigned)ntiles), dim3(256), st, a);
-    else launch(c, KID_syr2k_mm, k_syr2k_mm<false>, dim3((unsigned)ntiles), dim3(256), st, a);
-  }
-  HIPCHK(end_call(c));
-  return 0;
-}
-
-// ---- products of the matrix itself with a dense block (front_symm.hip) -----------------------------------------------
-// The contribution index (specified by the numpy restatement of tests/symm_ref.py): the items (k, r, p) in ascending
-// order with the base of each in `pos`, row i of C owning the positions [tptr[i], tptr[i + 1]) with its partials in
-// ascending (k, side, r, p).  Host only; with tptr == nullptr it counts the positions and builds nothing.
-static int64_t symm_index(const Symbolic& S, std::vector<int64_t>* tptr, std::vector<int32_t>* pos, std::vector<int32_t>* items) {
-  int64_t ntot = 0;
-  if (tptr) tptr->assign((size_t)S.n + 1, 0);
-  auto each = [&](int64_t k, auto f) {            // f(r, p, rows of the chunk, columns with a column partial)
-    const int64_t nf = S.nf(k), nn = S.nn(k);
-    for (int64_t r = 0; r < (nf + SYMM_ROWS - 1) / SYMM_ROWS; ++r)
-      for (int64_t p = 0; p < (nn + SYMM_KP - 1) / SYMM_KP; ++p) {
-        const int64_t last = std::min<int64_t>(r * SYMM_ROWS + SYMM_ROWS, nf) - 1;
-        if (p * SYMM_KP > last) continue;         // the chunk lies above the diagonal of this part
-        f(r, p, last - r * SYMM_ROWS + 1, std::max<int64_t>(0, std::min(std::min<int64_t>(nn, p * SYMM_KP + SYMM_KP), last) - p * SYMM_KP));
-      }
-  };
-  for (int64_t k = 0; k < S.nsn; ++k)
-    each(k, [&](int64_t r, int64_t p, int64_t nrows, int64_t ncol) {
-      if (tptr) {
-        if (ntot < ((int64_t)1 << 31)) { items->push_back((int32_t)k); items->push_back((int32_t)r); items->push_back((int32_t)p); items->push_back((int32_t)ntot); }
-        for (int64_t j = 0; j < nrows; ++j) ++(*tptr)[(size_t)S.rowidx[S.rowptr[k] + r * SYMM_ROWS + j] + 1];
-        for (int64_t j = 0; j < ncol; ++j) ++(*tptr)[(size_t)(S.snptr[k] + p * SYMM_KP + j) + 1];
-      }
-      ntot += nrows + ncol;
-    });
-  if (!tptr || ntot >= ((int64_t)1 << 31)) return ntot;
-  for (int64_t i = 0; i < S.n; ++i) (*tptr)[(size_t)i + 1] += (*tptr)[(size_t)i];
-  pos->assign((size_t)ntot, 0);
-  std::vector<int64_t> fill(tptr->begin(), tptr->end() - 1);
-  size_t it0 = 0;
-  for (int64_t k = 0; k < S.nsn; ++k) {           // ascending (k, side, r, p): the order of the sums of k_symm_combine
-    size_t it = it0;
-    each(k, [&](int64_t r, int64_t, int64_t nrows, int64_t) {
-      const int64_t base = (*items)[4 * it + 3];
-      for (int64_t j = 0; j < nrows; ++j) (*pos)[(size_t)(base + j)] = (int32_t)fill[(size_t)S.rowidx[S.rowptr[k] + r * SYMM_ROWS + j]]++;
-      ++it;
-    });
-    it = it0;
-    each(k, [&](int64_t, int64_t p, int64_t nrows, int64_t ncol) {
-      const int64_t base = (*items)[4 * it + 3] + nrows;
-      for (int64_t j = 0; j < ncol; ++j) (*pos)[(size_t)(base + j)] = (int32_t)fill[(size_t)(S.snptr[k] + p * SYMM_KP + j)]++;
-      ++it;
-    });
-    it0 = it;
-  }
-  return ntot;
-}
-
-int64_t csp_symm_positions(csp_ctx* c) {
-  if (!c) return SMCP_EINVAL;
-  if (c->D.symm_ntot < 0) c->D.symm_ntot = symm_index(c->S, nullptr, nullptr, nullptr);
-  return c->D.symm_ntot;
-}
-
-// Once per context: the index on the device, the rows with more than SYMM_HEAVY partials, and the item list with the
-// large fronts first (the long items start first), the widest front first among them.
-static int symm_setup(csp_ctx* c) {
-  DeviceCtx& D = c->D;
-  if (D.symm_tptr) return 0;
-  const Symbolic& S = c->S;
-  std::vector<int64_t> tptr;
-  std::vector<int32_t> pos, byk;
-  const int64_t ntot = symm_index(S, &tptr, &pos, &byk);
-  if (ntot >= ((int64_t)1 << 31)) return SMCP_EINVAL;                 // positions are 32-bit
-  D.symm_ntot = ntot;
-  std::vector<int32_t> heavy;
-  for (int64_t i = 0; i < S.n; ++i) if (tptr[(size_t)i + 1] - tptr[(size_t)i] > SYMM_HEAVY) heavy.push_back((int32_t)i);
-  std::vector<size_t> kfirst((size_t)S.nsn + 1, byk.size() / 4);
-  for (size_t it = byk.size() / 4; it-- > 0;) kfirst[(size_t)byk[4 * it]] = it;
-  for (int64_t k = S.nsn - 1; k >= 0; --k) kfirst[(size_t)k] = std::min(kfirst[(size_t)k], kfirst[(size_t)k + 1]);
-  std::vector<int64_t> order;
-  for (int pass = 1; pass >= 0; --pass)
-    for (int64_t k = 0; k < S.nsn; ++k) if ((c->large_mask[(size_t)k] != 0) == (pass == 1)) order.push_back(k);
-  std::stable_sort(order.begin(), order.begin() + D.nII_total, [&](int64_t x, int64_t y) { return S.nf(x) > S.nf(y); });
-  std::vector<int32_t> items;
-  items.reserve(byk.size());
-  for (size_t x = 0; x < order.size(); ++x) {
-    const size_t k = (size_t)order[x];
-    items.insert(items.end(), byk.begin() + 4 * kfirst[k], byk.begin() + 4 * kfirst[k + 1]);
-    if ((int64_t)x + 1 == D.nII_total) D.symm_nitems[0] = (int64_t)items.size() / 4;
-  }
-  D.symm_nitems[1] = (int64_t)items.size() / 4;
-  int rc = 0;
-  if ((rc = dev_upload(&D.symm_pos, pos, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.symm_heavy, heavy, D.bytes))) return rc;
-  D.symm_nheavy = (int64_t)heavy.size();
-  if ((rc = dev_upload(&D.symm_items, items, D.bytes))) return rc;
-  return dev_upload(&D.symm_tptr, tptr, D.bytes);
-}
-
-int csp_symm(csp_ctx* c, const double* X, const double* B, int64_t ldb, double* C, int64_t ldc, int64_t nrhs, double alpha, double beta,
-             void* stream) {
-  if (int rc = ready(c)) return rc;
-  const int mm = sw_int("SMCP_SYMM_MM", 1);       // read on every call: tools/symm_time.py alternates the settings in one process
-  DeviceCtx& D = c->D;
-  const Symbolic& S = c->S;
-  // (grid limits of the column-block dimension; a partitioned context holds valid panels on its own cliques only)
-  if (nrhs < 1 || nrhs > ((int64_t)1 << 18) || ldb < S.n || ldc < S.n || c->xr_world > 1) return SMCP_EINVAL;
-  {
-    const uintptr_t b0 = (uintptr_t)B, b1 = (uintptr_t)(B + ldb * (nrhs - 1) + S.n);
-    const uintptr_t c0 = (uintptr_t)C, c1 = (uintptr_t)(C + ldc * (nrhs - 1) + S.n);
-    if (c0 < b1 && b0 < c1) return SMCP_EINVAL;   // phase 2 would write what phase 1 of a later column block still reads
-  }
-  if (int rc = symm_setup(c)) return rc;
-  if (D.symm_ntot * nrhs > D.max_rhs * D.tmplen) return SMCP_ENOMEM;
-  hipStream_t st = (hipStream_t)stream;
-  // tile products for the large fronts from eight columns on and for every front from SYMM_MM_ALL columns on (the gates of
-  // csp_trmm); everything else, and everything on the generic / deterministic route, on the FMA kernel
-  const bool mm_ok = mm && !use_generic(c) && use_large();
-  const bool tiles_all = mm_ok && mm != 2 && nrhs >= SYMM_MM_ALL;
-  const bool tiles = tiles_all || (mm_ok && (nrhs >= 8 || mm == 2) && D.symm_nitems[0] > 0);
-  SymmArgs a;
-  a.cl = D.cl; a.rowidx = D.rowidx; a.items = D.symm_items; a.pos = D.symm_pos;
-  a.X = X; a.B = B; a.U = D.tmp; a.ntot = D.symm_ntot; a.nrhs = (int)nrhs; a.ldb = ldb;
-  if (alpha != 0.0) {                             // alpha == 0: neither X nor B is read
-    a.item0 = tiles_all ? 0 : tiles ? (int)D.symm_nitems[0] : 0;
-    a.nitems = tiles_all ? 0 : (int)D.symm_nitems[1] - a.item0;
-    auto fma = [&](auto cb) {      // CB columns of B per wave: X is read once per block of CB columns
-      constexpr int CB = decltype(cb)::value;
-      const dim3 grid((unsigned)((a.nitems + SYMM_WAVES - 1) / SYMM_WAVES), (unsigned)((a.nrhs + CB - 1) / CB));
-      launch(c, KID_symm_fma, k_symm_fma<CB>, grid, dim3(64 * SYMM_WAVES), st, a);
-    };
-    if (a.nitems) {
-      if (nrhs == 1) fma(std::integral_constant<int, 1>{});
-      else if (nrhs <= 4) fma(std::integral_constant<int, 4>{});
-      else fma(std::integral_constant<int, 8>{});
-    }
-    if (tiles) {
-      a.item0 = 0;
-      a.nitems = (int)D.symm_nitems[tiles_all ? 1 : 0];
-      launch(c, KID_symm_mm, k_symm_mm, dim3((unsigned)a.nitems, (unsigned)tiles64((int)nrhs)), dim3(256), st, a);
-    }
-  }
-  {
-    const int64_t cap = 16 * (int64_t)D.ncu;
-    const int light = (int)std::min<int64_t>((S.n * nrhs + 255) / 256, cap);
-    const int64_t nheavy = alpha != 0.0 ? D.symm_nheavy : 0;
-    const int hw = (int)std::min<int64_t>((nheavy * nrhs + 3) / 4, cap);
-    launch(c, KID_symm_combine, k_symm_combine, dim3((unsigned)(light + hw)), dim3(256), st, (const int64_t*)D.symm_tptr,
-           (const int32_t*)D.symm_heavy, (int)nheavy, light, (const double*)D.tmp, a.ntot, C, S.n, (int)nrhs, ldc, alpha, beta);
-  }
-  HIPCHK(end_call(c));
-  return 0;
-}
-
-// ---- minimum-rank completion (front_mrc.hip) ----------------------------------------------------------------------
-constexpr int64_t MRC_LDS = 128 * 1024;     // bytes of dynamic LDS a slot may take (the rest: the reduction buffers, one
-                                            // pair per instantiation of mrc_argmax)
-constexpr int64_t MRC_HBM_DOUBLES = (int64_t)1 << 25;  // HBM slots of one launch: 256 MiB at most (always at least one slot)
-
-static int mrc_setup(csp_ctx* c) {
-  DeviceCtx& D = c->D;
-  if (D.mrc_int) return 0;
-  if (int rc = dev_alloc(&D.mrc_int, 2 * c->S.nsn + 4, D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.mrc_xdiag, c->S.n, D.bytes)) return rc;
-  return dev_alloc(&D.mrc_list, c->S.nsn, D.bytes);
-}
-
-extern "C++" {
-// Runs kern over the cliques list[b, e) (host copy; the device copy is D.mrc_list), which ascend in slot size need[]
-// (doubles): those whose slot fits in LDS one workgroup each, in launches by size class, the rest over HBM slots
-template <class K>
-static int mrc_launch(csp_ctx* c, int kid, K kern, MrcArgs a, const std::vector<int64_t>& need, int64_t b, int64_t e,
-                      hipStream_t st) {
-  DeviceCtx& D = c->D;
-  static const bool attr = hipFuncSetAttribute((const void*)k_mrc_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS) == hipSuccess &&
-                           hipFuncSetAttribute((const void*)k_mrc_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS) == hipSuccess;
-  const int64_t lds_max = attr ? MRC_LDS : 65536;
-  int64_t q = b;
-  for (int64_t cap : {(int64_t)8192, (int64_t)16384, (int64_t)32768, (int64_t)65536, MRC_LDS}) {
-    int64_t q2 = q;
-    while (q2 < e && need[q2] * (int64_t)sizeof(double) <= std::min(cap, lds_max)) ++q2;
-    if (q2 > q) {
-      a.lev = D.mrc_list + q;
-      a.cnt = (int)(q2 - q);
-      a.ws = nullptr;
-      launch_lds(c, kid, kern, dim3((unsigned)(q2 - q)), dim3(MRC_NT), (size_t)need[q2 - 1] * sizeof(double), st, a);
-    }
-    q = q2;
-  }
-  if (q < e) {
-    const int64_t slot = (need[e - 1] + 31) / 32 * 32;
-    const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
-    if (G * slot > D.mrc_cap) {
-      if (D.mrc_ws) {
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipFree(D.mrc_ws));
-        D.bytes -= D.mrc_cap * (int64_t)sizeof(double);
-        D.mrc_ws = nullptr;
-        D.mrc_cap = 0;
-      }
-      if (int rc = dev_alloc(&D.mrc_ws, G * slot, D.bytes)) return rc;
-      D.mrc_cap = G * slot;
-    }
-    a.lev = D.mrc_list + q;
-    a.cnt = (int)(e - q);
-    a.ws = D.mrc_ws;
-    a.slot = slot;
-    launch(c, kid, kern, dim3((unsigned)G), dim3(MRC_NT), st, a);
-  }
-  return 0;
-}
-}  // extern "C++"
-
-// the cliques of every launch of a pass, each launch's range sorted by slot size, uploaded to D.mrc_list; ranges[l] ..
-// ranges[l + 1] is launch l.  r < 0: pass 1 (one launch over all cliques), else pass 2 (one launch per level, root first)
-static int mrc_lists(csp_ctx* c, int64_t r, std::vector<int64_t>& need, std::vector<int64_t>& ranges, hipStream_t st) {
-  const Symbolic& S = c->S;
-  std::vector<int32_t> list;
-  std::vector<std::pair<int64_t, int32_t>> tmp;
-  need.clear();
-  ranges.assign(1, 0);
-  auto add = [&](int64_t b, int64_t e) {
-    tmp.clear();
-    for (int64_t q = b; q < e; ++q) {
-      const int64_t k = S.levidx[q];
-      tmp.push_back({r < 0 ? mrc_slot1(S.nf(k)) : mrc_slot2(S.nn(k), S.na(k), r), (int32_t)k});
-    }
-    std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
-    ranges.push_back((int64_t)list.size());
-  };
-  if (r < 0) add(0, S.nsn);
-  else
-    for (int64_t l = S.nlev - 1; l >= 0; --l) add(S.levptr[l], S.levptr[l + 1]);
-  HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
-  return 0;
-}
-
-static MrcArgs mrc_args(csp_ctx* c, const double* x, double tol) {
-  MrcArgs a{};
-  a.cl = c->D.cl;
-  a.rowidx = c->D.rowidx;
-  a.x = x;
-  a.upd = c->D.upd;
-  a.xdiag = c->D.mrc_xdiag;
-  a.tol = tol;
-  a.rank = c->D.mrc_int;
-  a.flag = c->D.mrc_int + c->S.nsn;
-  return a;
-}
-
-// k_mrc_reduce and the read-back of its three integers
-static int mrc_reduce(csp_ctx* c, hipStream_t st, int32_t* out) {
-  int32_t* dout = c->D.mrc_int + 2 * c->S.nsn;
-  launch(c, KID_mrc_reduce, k_mrc_reduce, dim3(1), dim3(MRC_NT), st, (const int32_t*)c->D.mrc_int,
-         (const int32_t*)(c->D.mrc_int + c->S.nsn), (int)c->S.nsn, dout);
-  HIPCHK(end_call(c));
-  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-int csp_mrcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
-  if (int rc = ready(c)) return rc;
-  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = mrc_setup(c)) return rc;
-  std::vector<int64_t> need, ranges;
-  if (int rc = mrc_lists(c, -1, need, ranges, st)) return rc;
-  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)c->S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc_xdiag);
-  gather_all(c, x, 0, 1, c->D.upd, st);          // X_AA of every clique
-  if (int rc = mrc_launch(c, KID_mrc_rank, k_mrc_rank, mrc_args(c, x, tol), need, 0, c->S.nsn, st)) return rc;
-  int32_t out[3];
-  if (int rc = mrc_reduce(c, st, out)) return rc;
-  if (out[1]) return out[1];
-  *r = out[0];
-  return 0;
-}
-
-int csp_mrcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
-  if (int rc = ready(c)) return rc;
-  if (!x || !(tol >= 0.0) || r < 0 || r > c->S.max_front || (r > 0 && (!Y || ldY < r)) || c->ntrial != 1) return SMCP_EINVAL;
-  if (r == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = mrc_setup(c)) return rc;
-  std::vector<int64_t> need, ranges;
-  if (int rc = mrc_lists(c, r, need, ranges, st)) return rc;
-  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)c->S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc_xdiag);
-  MrcArgs a = mrc_args(c, x, tol);
-  a.Y = Y;
-  a.ldY = ldY;
-  a.r = (int)r;
-  for (size_t l = 0; l + 1 < ranges.size(); ++l)
-    if (int rc = mrc_launch(c, KID_mrc_factor, k_mrc_factor, a, need, ranges[l], ranges[l + 1], st)) return rc;
-  HIPCHK(hipMemsetAsync(c->D.mrc_int, 0, c->S.nsn * sizeof(int32_t), st));      // (k_mrc_reduce: ranks unused here)
-  int32_t out[3];
-  if (int rc = mrc_reduce(c, st, out)) return rc;
-  c->mrc_clamped = out[2];
-  return 0;
-}
-
-int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t trials, const double* G, int64_t nedges,
-                    const int64_t* ei, const int64_t* ej, const double* w, int8_t* s, double* cut, void* stream) {
-  if (int rc = ready(c)) return rc;
-  const int64_t n = c->S.n;
-  if (r < 1 || ldY < r || trials < 1 || trials > 65535 || nedges < 0 || !Y || !G || !s || !cut || (nedges && (!ei || !ej || !w)))
-    return SMCP_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  launch(c, KID_cut_signs, k_cut_signs, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)trials), dim3(MRC_NT), st, n, (int)r,
-         Y, ldY, G, s);
-  launch(c, KID_cut_weights, k_cut_weights, dim3((unsigned)trials), dim3(MRC_NT), st, n, nedges, ei, ej, w, (const int8_t*)s, cut);
-  HIPCHK(end_call(c));
-  return 0;
-}
-
-// ---- Euclidean distance matrix completion (front_edm.hip) -----------------------------------------------------------
-// The launches, slots and per-clique buffers are those of the minimum-rank completion (mrc_launch, D.mrc_*); only the
-// pass-2 slot is larger (edm_slot2), so the clique lists are built here.
-
-// edm_lists: mrc_lists with the slot sizes of front_edm.hip
-static int edm_lists(csp_ctx* c, int64_t r, std::vector<int64_t>& need, std::vector<int64_t>& ranges, hipStream_t st) {
-  const Symbolic& S = c->S;
-  std::vector<int32_t> list;
-  std::vector<std::pair<int64_t, int32_t>> tmp;
-  need.clear();
-  ranges.assign(1, 0);
-  auto add = [&](int64_t b, int64_t e) {
-    tmp.clear();
-    for (int64_t q = b; q < e; ++q) {
-      const int64_t k = S.levidx[q];
-      tmp.push_back({r < 0 ? mrc_slot1(S.nf(k)) : edm_slot2(S.nn(k), S.na(k), r), (int32_t)k});
-    }
-    std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
-    ranges.push_back((int64_t)list.size());
-  };
-  if (r < 0) add(0, S.nsn);
-  else
-    for (int64_t l = S.nlev - 1; l >= 0; --l) add(S.levptr[l], S.levptr[l + 1]);
-  HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
-  return 0;
-}
-
-// the LDS limit mrc_launch assumes for its own kernels, granted to the two of this file as well
-static void edm_lds_attr() {
-  static const bool once = (hipFuncSetAttribute((const void*)k_edm_rank, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS),
-                            hipFuncSetAttribute((const void*)k_edm_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS),
-                            true);
-  (void)once;
-}
-
-// k_edm_reduce and the read-back of its three integers
-static int edm_reduce(csp_ctx* c, hipStream_t st, int32_t* out) {
-  int32_t* dout = c->D.mrc_int + 2 * c->S.nsn;
-  launch(c, KID_edm_reduce, k_edm_reduce, dim3(1), dim3(MRC_NT), st, (const int32_t*)c->D.mrc_int,
-         (const int32_t*)(c->D.mrc_int + c->S.nsn), (int)c->S.nsn, dout);
-  HIPCHK(end_call(c));
-  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
-  return 0;
-}
-
-int csp_edmcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
-  if (int rc = ready(c)) return rc;
-  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = mrc_setup(c)) return rc;
-  edm_lds_attr();
-  std::vector<int64_t> need, ranges;
-  if (int rc = edm_lists(c, -1, need, ranges, st)) return rc;
-  gather_all(c, x, 0, 1, c->D.upd, st);          // D_AA of every clique
-  if (int rc = mrc_launch(c, KID_edm_rank, k_edm_rank, mrc_args(c, x, tol), need, 0, c->S.nsn, st)) return rc;
-  int32_t out[3];
-  if (int rc = edm_reduce(c, st, out)) return rc;
-  if (out[2]) return SMCP_EINVAL;                 // a nonzero diagonal entry
-  if (out[1]) return out[1];
-  *r = out[0];
-  return 0;
-}
-
-int csp_edmcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
-  if (int rc = ready(c)) return rc;
-  if (!x || !(tol >= 0.0) || r < 0 || r > c->S.max_front || (r > 0 && (!Y || ldY < r)) || c->ntrial != 1) return SMCP_EINVAL;
-  c->edm_clamped = 0;
-  if (r == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (int rc = mrc_setup(c)) return rc;
-  edm_lds_attr();
-  std::vector<int64_t> need, ranges;
-  if (int rc = edm_lists(c, r, need, ranges, st)) return rc;
-  MrcArgs a = mrc_args(c, x, tol);
-  a.Y = Y;
-  a.ldY = ldY;
-  a.r = (int)r;
-  for (size_t l = 0; l + 1 < ranges.size(); ++l)
-    if (int rc = mrc_launch(c, KID_edm_factor, k_edm_factor, a, need, ranges[l], ranges[l + 1], st)) return rc;
-  HIPCHK(hipMemsetAsync(c->D.mrc_int, 0, c->S.nsn * sizeof(int32_t), st));      // (k_mrc_reduce: ranks unused here)
-  int32_t out[3];
-  if (int rc = mrc_reduce(c, st, out)) return rc;
-  c->edm_clamped = out[2];
-  return 0;
-}
-
-int csp_edm_dense(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, const int64_t* perm, double* D, int64_t ldD,
-                  void* stream) {
-  if (int rc = ready(c)) return rc;
-  const int64_t n = c->S.n;
-  if (r < 0 || r > INT32_MAX || (r > 0 && (!Y || ldY < r)) || !D || ldD < n) return SMCP_EINVAL;
-  if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned nt = (unsigned)((n + EDM_TILE - 1) / EDM_TILE);
-  if (nt > 65535) return SMCP_EINVAL;
-  launch(c, KID_edm_dense, k_edm_dense, dim3(nt, nt), dim3(MRC_NT), st, n, (int)r, Y, ldY, perm, D, ldD);
-  HIPCHK(end_call(c));
-  return 0;
-}
-
-// ---- dense maximum-determinant PSD completion (front_psd.hip) -------------------------------------------------------
-// ulist (the columns in the order the levels complete them, root level first, cliques ascending inside a level), the tile
-// tasks of the two fill launches of every level and the W workspace: built on the first call
-static int psd_setup(csp_ctx* c, hipStream_t st) {
-  DeviceCtx& D = c->D;
-  if (D.psd_ulist) return 0;
-  const Symbolic& S = c->S;
-  std::vector<int32_t> ulist;
-  std::vector<PsdTask> tasks;
-  std::vector<int64_t> end_of(S.nsn, 0);
-  c->psd_lev.clear();
-  const int64_t max_tasks = (int64_t)1 << 26;
-  for (int64_t l = S.nlev - 1; l >= 0; --l) {
-    std::vector<int64_t> ks(S.levidx.begin() + S.levptr[l], S.levidx.begin() + S.levptr[l + 1]);
-    std::sort(ks.begin(), ks.end());
-    const int64_t before = (int64_t)ulist.size();
-    for (int64_t k : ks) {
-      for (int64_t j = S.snptr[k]; j < S.snptr[k + 1]; ++j) ulist.push_back((int32_t)j);
-      end_of[k] = (int64_t)ulist.size();
-    }
-    const int64_t after = (int64_t)ulist.size();
-    csp_ctx::PsdLevel L;
-    auto add = [&](int64_t k, int64_t b, int64_t e) {
-      for (int64_t off = b; off < e; off += LT)
-        for (int64_t n0 = 0; n0 < S.nn(k); n0 += LT)
-          tasks.push_back({(int32_t)k, (int32_t)off, (int32_t)std::min<int64_t>(LT, e - off), (int32_t)n0});
-    };
-    L.b1 = (int64_t)tasks.size();
-    for (int64_t k : ks) if (S.na(k) > 0) add(k, 0, before);                 // step 1: the rows of the levels done
-    L.b2 = (int64_t)tasks.size();
-    for (int64_t k : ks) if (S.na(k) > 0) add(k, end_of[k], after);          // step 2: the later cliques of the level
-    L.e2 = (int64_t)tasks.size();
-    if (L.e2 > max_tasks) return SMCP_ENOMEM;
-    if (L.e2 > L.b1) c->psd_lev.push_back(L);
-  }
-  if (int rc = dev_alloc(&D.psd_tasks, (int64_t)tasks.size(), D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.psd_w, S.blklen(), D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.psd_idx, S.sepptr[S.nsn], D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.psd_ra, S.nsn, D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.psd_ulist, S.n, D.bytes)) return rc;
-  if (!tasks.empty()) HIPCHK(hipMemcpyAsync(D.psd_tasks, tasks.data(), tasks.size() * sizeof(PsdTask), hipMemcpyHostToDevice, st));
-  if (!ulist.empty()) HIPCHK(hipMemcpyAsync(D.psd_ulist, ulist.data(), ulist.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));      // (host temporaries)
-  return 0;
-}
-
-// the cliques with a separator, ascending in slot size, uploaded to D.mrc_list
-static int psd_lists(csp_ctx* c, std::vector<int64_t>& need, hipStream_t st) {
-  const Symbolic& S = c->S;
-  std::vector<std::pair<int64_t, int32_t>> tmp;
-  for (int64_t k = 0; k < S.nsn; ++k)
-    if (S.na(k) > 0) tmp.push_back({psd_slot(S.na(k)), (int32_t)k});
-  std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-  std::vector<int32_t> list;
-  need.clear();
-  for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
-  if (!list.empty()) HIPCHK(hipMemcpyAsync(c->D.mrc_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
-  return 0;
-}
-
-int csp_psdcompletion(csp_ctx* c, const double* x, double tol, double* Xd, int64_t ldX, void* stream) {
-  if (int rc = ready(c)) return rc;
-  const int64_t n = c->S.n, nsn = c->S.nsn;
-  if (!x || !Xd || !(tol >= 0.0) || ldX < n || c->ntrial != 1) return SMCP_EINVAL;
-  if (n == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  DeviceCtx& D = c->D;
-  if (int rc = mrc_setup(c)) return rc;
-  if (int rc = psd_setup(c, st)) return rc;
-  static const bool attr = (hipFuncSetAttribute((const void*)k_psd_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS), true);
-  (void)attr;
-  // is every clique block positive semidefinite?  (pass 1 of the minimum-rank completion)
-  std::vector<int64_t> need, ranges;
-  if (int rc = mrc_lists(c, -1, need, ranges, st)) return rc;
-  launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)nsn), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, x, D.mrc_xdiag);
-  gather_all(c, x, 0, 1, D.upd, st);          // X_AA of every clique
-  MrcArgs a = mrc_args(c, x, tol);
-  if (int rc = mrc_launch(c, KID_mrc_rank, k_mrc_rank, a, need, 0, nsn, st)) return rc;
-  int32_t out[3];
-  if (int rc = mrc_reduce(c, st, out)) return rc;
-  if (out[1]) return out[1];
-  launch(c, KID_psd_zero, k_psd_zero, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)std::min<int64_t>(n, 1024)), dim3(MRC_NT), st,
-         n, Xd, ldX);
-  launch(c, KID_psd_scatter, k_psd_scatter, dim3((unsigned)nsn), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const int32_t*)D.rowidx, x,
-         Xd, ldX);
-  if (int rc = psd_lists(c, need, st)) return rc;
-  a.pw = D.psd_w;
-  a.pidx = D.psd_idx;
-  a.pra = D.psd_ra;
-  if (int rc = mrc_launch(c, KID_psd_solve, k_psd_solve, a, need, 0, (int64_t)need.size(), st)) return rc;
-  PsdFillArgs f{D.cl, D.rowidx, nullptr, D.psd_ulist, D.psd_w, D.psd_idx, D.psd_ra, Xd, ldX};
-  for (const csp_ctx::PsdLevel& L : c->psd_lev) {
-    if (L.b2 > L.b1) {
-      f.tasks = D.psd_tasks + L.b1;
-      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.b2 - L.b1)), dim3(256), st, f);
-    }
-    if (L.e2 > L.b2) {
-      f.tasks = D.psd_tasks + L.b2;
-      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.e2 - L.b2)), dim3(256), st, f);
-    }
-  }
-  HIPCHK(end_call(c));
-  return 0;
-}
+extern "C" {
 
 static int reduce_impl(csp_ctx* c, const double* X, const double* Y, int mode, double* out, hipStream_t st) {
   int nb = 512;

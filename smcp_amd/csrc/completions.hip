@@ -1,0 +1,317 @@
+// Host drivers of the completions: minimum-rank (front_mrc.hip, with the cut rounding of csp_maxcut_cuts), Euclidean
+// distance matrix (front_edm.hip, with csp_edm_dense) and dense maximum-determinant PSD (front_psd.hip).  Included by
+// capi.hip.  All three share the launches, slots and per-clique buffers of D.mrc (CompletionWs, context.hpp): a rank pass
+// over all cliques at once, then either a factor pass, one launch group per level from the root down (mrc, edm), or the
+// solves and fills of the dense completion (psd).
+
+namespace {
+
+constexpr int64_t MRC_LDS = 128 * 1024;     // bytes of dynamic LDS a slot may take (the rest: the reduction buffers, one
+                                            // pair per instantiation of mrc_argmax)
+constexpr int64_t MRC_HBM_DOUBLES = (int64_t)1 << 25;  // HBM slots of one launch: 256 MiB at most (always at least one slot)
+
+int mrc_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  if (D.mrc.ints) return 0;
+  if (int rc = dev_alloc(&D.mrc.ints, 2 * c->S.nsn + 4, D.bytes)) return rc;
+  if (int rc = dev_alloc(&D.mrc.xdiag, c->S.n, D.bytes)) return rc;
+  return dev_alloc(&D.mrc.list, c->S.nsn, D.bytes);
+}
+
+// bytes of dynamic LDS a launch of Kern may ask for: MRC_LDS once the device has granted it to this kernel (asked on
+// its first launch), the default limit otherwise
+template <auto Kern>
+int64_t lds_ceiling() {
+  static const bool granted = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MRC_LDS) == hipSuccess;
+  return granted ? MRC_LDS : 65536;
+}
+
+// Runs Kern over the cliques list[b, e) (host copy; the device copy is D.mrc.list), which ascend in slot size need[]
+// (doubles): those whose slot fits in LDS one workgroup each, in launches by size class, the rest over HBM slots
+template <auto Kern>
+int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need, int64_t b, int64_t e, hipStream_t st) {
+  DeviceCtx& D = c->D;
+  const int64_t lds_max = lds_ceiling<Kern>();
+  int64_t q = b;
+  for (int64_t cap : {(int64_t)8192, (int64_t)16384, (int64_t)32768, (int64_t)65536, MRC_LDS}) {
+    int64_t q2 = q;
+    while (q2 < e && need[q2] * (int64_t)sizeof(double) <= std::min(cap, lds_max)) ++q2;
+    if (q2 > q) {
+      a.lev = D.mrc.list + q;
+      a.cnt = (int)(q2 - q);
+      a.ws = nullptr;
+      launch_lds(c, kid, Kern, dim3((unsigned)(q2 - q)), dim3(MRC_NT), (size_t)need[q2 - 1] * sizeof(double), st, a);
+    }
+    q = q2;
+  }
+  if (q < e) {
+    const int64_t slot = (need[e - 1] + 31) / 32 * 32;
+    const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
+    if (int rc = dev_grow(&D.mrc.ws, &D.mrc.cap, G * slot, D.bytes, st)) return rc;
+    a.lev = D.mrc.list + q;
+    a.cnt = (int)(e - q);
+    a.ws = D.mrc.ws;
+    a.slot = slot;
+    launch(c, kid, Kern, dim3((unsigned)G), dim3(MRC_NT), st, a);
+  }
+  return 0;
+}
+
+// The cliques of every launch group of a pass, uploaded to D.mrc.list: group l is launches[l] (a range of clique numbers)
+// without the cliques whose slot(k) is negative, in ascending slot size (doubles; ties keep their order), and occupies
+// ranges[l] .. ranges[l + 1] of the list and of need[]
+using CliqueRange = std::pair<const int64_t*, const int64_t*>;
+template <class Slot>
+int slot_sorted_lists(csp_ctx* c, const std::vector<CliqueRange>& launches, Slot slot, std::vector<int64_t>& need,
+                      std::vector<int64_t>& ranges, hipStream_t st) {
+  std::vector<int32_t> list;
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  need.clear();
+  ranges.assign(1, 0);
+  for (const CliqueRange& L : launches) {
+    tmp.clear();
+    for (const int64_t* k = L.first; k != L.second; ++k)
+      if (slot(*k) >= 0) tmp.push_back({slot(*k), (int32_t)*k});
+    std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    for (auto& t : tmp) { need.push_back(t.first); list.push_back(t.second); }
+    ranges.push_back((int64_t)list.size());
+  }
+  if (!list.empty()) HIPCHK(hipMemcpyAsync(c->D.mrc.list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(hipStreamSynchronize(st));      // (list is a host temporary)
+  return 0;
+}
+// pass 1: one launch group over all cliques
+std::vector<CliqueRange> all_cliques(const Symbolic& S) { return {{S.levidx.data(), S.levidx.data() + S.nsn}}; }
+// pass 2: one launch group per level, root first
+std::vector<CliqueRange> levels_root_first(const Symbolic& S) {
+  std::vector<CliqueRange> v;
+  for (int64_t l = S.nlev - 1; l >= 0; --l) v.push_back({S.levidx.data() + S.levptr[l], S.levidx.data() + S.levptr[l + 1]});
+  return v;
+}
+
+MrcArgs mrc_args(csp_ctx* c, const double* x, double tol) {
+  MrcArgs a{};
+  a.cl = c->D.cl;
+  a.rowidx = c->D.rowidx;
+  a.x = x;
+  a.upd = c->D.upd;
+  a.xdiag = c->D.mrc.xdiag;
+  a.tol = tol;
+  a.rank = c->D.mrc.ints;
+  a.flag = c->D.mrc.ints + c->S.nsn;
+  return a;
+}
+
+// a reduce kernel (k_mrc_reduce, k_edm_reduce) over the per-clique ranks and flags, and the read-back of its three integers
+template <class K>
+int reduce_flags(csp_ctx* c, int kid, K kern, hipStream_t st, int32_t* out) {
+  int32_t* ints = c->D.mrc.ints;
+  int32_t* dout = ints + 2 * c->S.nsn;
+  launch(c, kid, kern, dim3(1), dim3(MRC_NT), st, (const int32_t*)ints, (const int32_t*)(ints + c->S.nsn), (int)c->S.nsn, dout);
+  HIPCHK(end_call(c));
+  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return 0;
+}
+
+// Pass 1 of a completion: Rank over every clique block in one launch group (their separator blocks gathered first), then
+// Reduce.  *r = the largest rank; a clique that fails the test of Rank returns its status.  with_diag: k_mrc_diag leaves
+// diag(X) for the thresholds (mrc, psd); out2_is_error: the third integer of Reduce flags invalid input (edm: a nonzero
+// diagonal entry).
+template <auto Rank, class R>
+int rank_pass(csp_ctx* c, const double* x, double tol, int kid_rank, int kid_reduce, R reduce, bool with_diag, bool out2_is_error,
+              int64_t* r, hipStream_t st) {
+  if (int rc = mrc_setup(c)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = slot_sorted_lists(c, all_cliques(c->S), [&](int64_t k) { return mrc_slot1(c->S.nf(k)); }, need, ranges, st)) return rc;
+  if (with_diag) launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)c->S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc.xdiag);
+  gather_all(c, x, 0, 1, c->D.upd, st);          // X_AA of every clique
+  if (int rc = mrc_launch<Rank>(c, kid_rank, mrc_args(c, x, tol), need, 0, c->S.nsn, st)) return rc;
+  int32_t out[3];
+  if (int rc = reduce_flags(c, kid_reduce, reduce, st, out)) return rc;
+  if (out2_is_error && out[2]) return SMCP_EINVAL;
+  if (out[1]) return out[1];
+  if (r) *r = out[0];
+  return 0;
+}
+
+// Pass 2 of a completion: Factor over the levels, root first, writing the r rows of Y; *clamped = the cliques whose Schur
+// factor lost columns to the r-column cap.  slot2(nn, na, r): the slot of a clique in doubles.
+template <auto Factor, class Slot2>
+int factor_pass(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, int kid, Slot2 slot2, bool with_diag,
+                int64_t* clamped, hipStream_t st) {
+  const Symbolic& S = c->S;
+  if (int rc = mrc_setup(c)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = slot_sorted_lists(c, levels_root_first(S), [&](int64_t k) { return slot2(S.nn(k), S.na(k), r); }, need, ranges, st)) return rc;
+  if (with_diag) launch(c, KID_mrc_diag, k_mrc_diag, dim3((unsigned)S.nsn), dim3(MRC_NT), st, (const CliqueDesc*)c->D.cl, x, c->D.mrc.xdiag);
+  MrcArgs a = mrc_args(c, x, tol);
+  a.Y = Y;
+  a.ldY = ldY;
+  a.r = (int)r;
+  for (size_t l = 0; l + 1 < ranges.size(); ++l)
+    if (int rc = mrc_launch<Factor>(c, kid, a, need, ranges[l], ranges[l + 1], st)) return rc;
+  // the clamped count is the third integer of k_mrc_reduce for both completions (k_edm_reduce counts nonzero diagonal
+  // entries there); its ranks are unused here
+  HIPCHK(hipMemsetAsync(c->D.mrc.ints, 0, S.nsn * sizeof(int32_t), st));
+  int32_t out[3];
+  if (int rc = reduce_flags(c, KID_mrc_reduce, k_mrc_reduce, st, out)) return rc;
+  *clamped = out[2];
+  return 0;
+}
+
+// what csp_mrcompletion and csp_edmcompletion refuse
+int factor_args_check(csp_ctx* c, const double* x, double tol, int64_t r, const double* Y, int64_t ldY) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !(tol >= 0.0) || r < 0 || r > c->S.max_front || (r > 0 && (!Y || ldY < r)) || c->ntrial != 1) return SMCP_EINVAL;
+  return 0;
+}
+
+// ---- dense maximum-determinant PSD completion (front_psd.hip) -------------------------------------------------------
+// ulist (the columns in the order the levels complete them, root level first, cliques ascending inside a level), the tile
+// tasks of the two fill launches of every level and the W workspace: built on the first call
+int psd_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  PsdPlan& P = D.psd;
+  if (P.ulist) return 0;
+  const Symbolic& S = c->S;
+  std::vector<int32_t> ulist;
+  std::vector<PsdTask> tasks;
+  std::vector<int64_t> end_of(S.nsn, 0);
+  c->psd_lev.clear();
+  const int64_t max_tasks = (int64_t)1 << 26;
+  for (int64_t l = S.nlev - 1; l >= 0; --l) {
+    std::vector<int64_t> ks(S.levidx.begin() + S.levptr[l], S.levidx.begin() + S.levptr[l + 1]);
+    std::sort(ks.begin(), ks.end());
+    const int64_t before = (int64_t)ulist.size();
+    for (int64_t k : ks) {
+      for (int64_t j = S.snptr[k]; j < S.snptr[k + 1]; ++j) ulist.push_back((int32_t)j);
+      end_of[k] = (int64_t)ulist.size();
+    }
+    const int64_t after = (int64_t)ulist.size();
+    csp_ctx::PsdLevel L;
+    auto add = [&](int64_t k, int64_t b, int64_t e) {
+      for (int64_t off = b; off < e; off += LT)
+        for (int64_t n0 = 0; n0 < S.nn(k); n0 += LT)
+          tasks.push_back({(int32_t)k, (int32_t)off, (int32_t)std::min<int64_t>(LT, e - off), (int32_t)n0});
+    };
+    L.b1 = (int64_t)tasks.size();
+    for (int64_t k : ks) if (S.na(k) > 0) add(k, 0, before);                 // step 1: the rows of the levels done
+    L.b2 = (int64_t)tasks.size();
+    for (int64_t k : ks) if (S.na(k) > 0) add(k, end_of[k], after);          // step 2: the later cliques of the level
+    L.e2 = (int64_t)tasks.size();
+    if (L.e2 > max_tasks) return SMCP_ENOMEM;
+    if (L.e2 > L.b1) c->psd_lev.push_back(L);
+  }
+  if (int rc = dev_upload(&P.tasks, tasks, D.bytes)) return rc;
+  if (int rc = dev_alloc(&P.w, S.blklen(), D.bytes)) return rc;
+  if (int rc = dev_alloc(&P.idx, S.sepptr[S.nsn], D.bytes)) return rc;
+  if (int rc = dev_alloc(&P.ra, S.nsn, D.bytes)) return rc;
+  return dev_upload(&P.ulist, ulist, D.bytes);      // last: ulist marks the plan as built
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- minimum-rank completion (front_mrc.hip) ----------------------------------------------------------------------
+int csp_mrcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
+  return rank_pass<k_mrc_rank>(c, x, tol, KID_mrc_rank, KID_mrc_reduce, k_mrc_reduce, true, false, r, (hipStream_t)stream);
+}
+
+int csp_mrcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
+  if (int rc = factor_args_check(c, x, tol, r, Y, ldY)) return rc;
+  if (r == 0) return 0;
+  return factor_pass<k_mrc_factor>(c, x, tol, r, Y, ldY, KID_mrc_factor, mrc_slot2, true, &c->mrc_clamped, (hipStream_t)stream);
+}
+
+int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t trials, const double* G, int64_t nedges,
+                    const int64_t* ei, const int64_t* ej, const double* w, int8_t* s, double* cut, void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int64_t n = c->S.n;
+  if (r < 1 || ldY < r || trials < 1 || trials > 65535 || nedges < 0 || !Y || !G || !s || !cut || (nedges && (!ei || !ej || !w)))
+    return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  launch(c, KID_cut_signs, k_cut_signs, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)trials), dim3(MRC_NT), st, n, (int)r,
+         Y, ldY, G, s);
+  launch(c, KID_cut_weights, k_cut_weights, dim3((unsigned)trials), dim3(MRC_NT), st, n, nedges, ei, ej, w, (const int8_t*)s, cut);
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- Euclidean distance matrix completion (front_edm.hip) -----------------------------------------------------------
+// Only the kernels and the pass-2 slot (edm_slot2, larger) differ from the minimum-rank completion; diag(D) = 0 is checked
+// by the reduce kernel, not read by the thresholds.
+int csp_edmcompletion_rank(csp_ctx* c, const double* x, double tol, int64_t* r, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !r || !(tol >= 0.0) || c->ntrial != 1) return SMCP_EINVAL;
+  return rank_pass<k_edm_rank>(c, x, tol, KID_edm_rank, KID_edm_reduce, k_edm_reduce, false, true, r, (hipStream_t)stream);
+}
+
+int csp_edmcompletion(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, void* stream) {
+  if (int rc = factor_args_check(c, x, tol, r, Y, ldY)) return rc;
+  c->edm_clamped = 0;
+  if (r == 0) return 0;
+  return factor_pass<k_edm_factor>(c, x, tol, r, Y, ldY, KID_edm_factor, edm_slot2, false, &c->edm_clamped, (hipStream_t)stream);
+}
+
+int csp_edm_dense(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, const int64_t* perm, double* D, int64_t ldD,
+                  void* stream) {
+  if (int rc = ready(c)) return rc;
+  const int64_t n = c->S.n;
+  if (r < 0 || r > INT32_MAX || (r > 0 && (!Y || ldY < r)) || !D || ldD < n) return SMCP_EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned nt = (unsigned)((n + EDM_TILE - 1) / EDM_TILE);
+  if (nt > 65535) return SMCP_EINVAL;
+  launch(c, KID_edm_dense, k_edm_dense, dim3(nt, nt), dim3(MRC_NT), st, n, (int)r, Y, ldY, perm, D, ldD);
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- dense maximum-determinant PSD completion (front_psd.hip) -------------------------------------------------------
+int csp_psdcompletion(csp_ctx* c, const double* x, double tol, double* Xd, int64_t ldX, void* stream) {
+  if (int rc = ready(c)) return rc;
+  const Symbolic& S = c->S;
+  const int64_t n = S.n, nsn = S.nsn;
+  if (!x || !Xd || !(tol >= 0.0) || ldX < n || c->ntrial != 1) return SMCP_EINVAL;
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  DeviceCtx& D = c->D;
+  if (int rc = mrc_setup(c)) return rc;
+  if (int rc = psd_setup(c)) return rc;
+  const PsdPlan& P = D.psd;
+  // is every clique block positive semidefinite?  (pass 1 of the minimum-rank completion)
+  if (int rc = rank_pass<k_mrc_rank>(c, x, tol, KID_mrc_rank, KID_mrc_reduce, k_mrc_reduce, true, false, nullptr, st)) return rc;
+  launch(c, KID_psd_zero, k_psd_zero, dim3((unsigned)((n + MRC_NT - 1) / MRC_NT), (unsigned)std::min<int64_t>(n, 1024)), dim3(MRC_NT), st,
+         n, Xd, ldX);
+  launch(c, KID_psd_scatter, k_psd_scatter, dim3((unsigned)nsn), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const int32_t*)D.rowidx, x,
+         Xd, ldX);
+  // the solves: the cliques with a separator (ascending, then by slot size)
+  std::vector<int64_t> ks((size_t)nsn), need, ranges;
+  for (int64_t k = 0; k < nsn; ++k) ks[(size_t)k] = k;
+  if (int rc = slot_sorted_lists(c, {{ks.data(), ks.data() + nsn}}, [&](int64_t k) { return S.na(k) > 0 ? psd_slot(S.na(k)) : (int64_t)-1; }, need, ranges, st))
+    return rc;
+  MrcArgs a = mrc_args(c, x, tol);
+  a.pw = P.w;
+  a.pidx = P.idx;
+  a.pra = P.ra;
+  if (int rc = mrc_launch<k_psd_solve>(c, KID_psd_solve, a, need, 0, (int64_t)need.size(), st)) return rc;
+  PsdFillArgs f{D.cl, D.rowidx, nullptr, P.ulist, P.w, P.idx, P.ra, Xd, ldX};
+  for (const csp_ctx::PsdLevel& L : c->psd_lev) {
+    if (L.b2 > L.b1) {
+      f.tasks = P.tasks + L.b1;
+      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.b2 - L.b1)), dim3(256), st, f);
+    }
+    if (L.e2 > L.b2) {
+      f.tasks = P.tasks + L.b2;
+      launch(c, KID_psd_fill, k_psd_fill, dim3((unsigned)(L.e2 - L.b2)), dim3(256), st, f);
+    }
+  }
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+}  // extern "C"

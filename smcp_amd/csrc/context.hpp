@@ -27,6 +27,72 @@ struct CliqueDesc {
 
 struct PsdTask;
 
+// frees the device buffers named and clears the pointers
+template <class... T>
+inline void dev_release(T*&... p) {
+  ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
+}
+
+// Plans of the operations of csrc/products.hip and csrc/completions.hip: built on the first call of each, released once by
+// csp_symbolic_destroy.
+// A transposed row index (null until built): row i of the result owns the positions [tptr[i], tptr[i + 1]) of a list of all
+// contributions, in the order of its sum; pos: producer's slot -> position; heavy: the rows with long sums
+struct RowIndex {
+  int64_t* tptr = nullptr; int32_t* pos = nullptr;
+  int32_t* heavy = nullptr; int64_t nheavy = 0;
+  void release() { dev_release(tptr, pos, heavy); }
+};
+
+// products with the factor (front_trmm.hip): the transposed separator index (the contributions are all separator entries, a
+// row's own in ascending clique; pos[sepptr[k] + q] = the position of entry q of clique k; heavy: more than TRMM_HEAVY), and
+// the (clique, chunk) items of the FMA kernels, per trans: the items of the large fronts come last ([t][0]: items without
+// them, [t][1]: all); the (clique, row tile) pairs of the tile products, per trans: those of the large fronts come FIRST
+// ([t][0]: theirs, [t][1]: all)
+struct TrmmPlan {
+  RowIndex idx;
+  int32_t* items[2] = {nullptr, nullptr}; int64_t nitems[2][2] = {{0, 0}, {0, 0}};
+  int32_t* tiles[2] = {nullptr, nullptr}; int64_t ntiles[2][2] = {{0, 0}, {0, 0}};
+  void release() { idx.release(); dev_release(items[0], items[1], tiles[0], tiles[1]); }
+};
+
+// rank-k updates on the pattern (front_syr2k.hip): (clique, row chunk, column chunk, zero) items of the FMA kernel, those of
+// the large fronts LAST ([0]: items without them, [1]: all), and (clique, row tile, column tile, zero) tiles of the tile
+// products, those of the large fronts FIRST ([0]: theirs, [1]: all); zero: all rows above the diagonal, only zeros are stored
+struct Syr2kPlan {
+  bool ready = false;
+  int32_t* items = nullptr; int64_t nitems[2] = {0, 0};
+  int32_t* tiles = nullptr; int64_t ntiles[2] = {0, 0};
+  void release() { dev_release(items, tiles); }
+};
+
+// products of the matrix itself (front_symm.hip): the contribution index (the contributions are all ntot partials; pos: per
+// item the positions of its row partials, then of its column partials; heavy: more than SYMM_HEAVY), and the (clique, row
+// chunk, column part, base in pos) items, those of the large fronts FIRST ([0]: theirs, [1]: all).  ntot: -1 until counted
+// (csp_symm_positions: host only)
+struct SymmPlan {
+  RowIndex idx;
+  int32_t* items = nullptr; int64_t nitems[2] = {0, 0};
+  int64_t ntot = -1;
+  void release() { idx.release(); dev_release(items); }
+};
+
+// minimum-rank, distance-matrix and dense PSD completion (front_mrc.hip, front_edm.hip, front_psd.hip): per-workgroup HBM
+// slots of the cliques too wide for LDS (ws, cap doubles), per clique rank and flag (2 nsn) + the reduced results (ints),
+// diag(X), and the cliques of every launch (list, sorted by slot size within a launch)
+struct CompletionWs {
+  double* ws = nullptr; int64_t cap = 0;
+  int32_t* ints = nullptr; double* xdiag = nullptr; int32_t* list = nullptr;
+  void release() { dev_release(ws, ints, xdiag, list); cap = 0; }
+};
+
+// dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
+// W_k[rho] (at its panel offset), the rows A[rho] (at its separator offset) and |rho|
+struct PsdPlan {
+  PsdTask* tasks = nullptr; int32_t* ulist = nullptr;
+  double* w = nullptr; int32_t* idx = nullptr; int32_t* ra = nullptr;
+  void release() { dev_release(tasks, ulist, w, idx, ra); }
+};
+
 struct DeviceCtx {
   int device = -1;
   int ncu = 256;           // compute units of the device (csp_device_init): launch heuristics
@@ -157,37 +223,11 @@ struct DeviceCtx {
   bool qr_valid = false;       // ustack holds Q and qr_ws the factor for the matrices (qr_L, qr_Y)
   const void* qr_L = nullptr; const void* qr_Y = nullptr;
   int64_t lfd_len = 0;         // doubles of lfd (large-front slots + the dense slot)
-  // minimum-rank completion (front_mrc.hip): per-workgroup HBM slots of the cliques too wide for LDS, per clique rank and
-  // flag (2 nsn) + the reduced results, diag(X), and the cliques of every launch (sorted by slot size within a launch)
-  double* mrc_ws = nullptr; int64_t mrc_cap = 0;
-  int32_t* mrc_int = nullptr; double* mrc_xdiag = nullptr; int32_t* mrc_list = nullptr;
-  // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
-  // W_k[rho] (at its panel offset), the rows A[rho] (at its separator offset) and |rho|
-  struct PsdTask* psd_tasks = nullptr; int32_t* psd_ulist = nullptr;
-  double* psd_w = nullptr; int32_t* psd_idx = nullptr; int32_t* psd_ra = nullptr;
-  // products with the factor (front_trmm.hip): the transposed separator index (row i of the matrix owns the positions
-  // [trmm_tptr[i], trmm_tptr[i + 1]) of a list of all separator entries, its own in ascending clique; trmm_pos[sepptr[k] + q] =
-  // the position of entry q of clique k), the rows with more than TRMM_HEAVY entries, and the (clique, chunk) items of the FMA
-  // kernels, per trans: the items of the large fronts come last ([t][0]: items without them, [t][1]: all); the (clique, row
-  // tile) pairs of the tile products, per trans: those of the large fronts come FIRST ([t][0]: theirs, [t][1]: all)
-  int64_t* trmm_tptr = nullptr; int32_t* trmm_pos = nullptr;
-  int32_t* trmm_heavy = nullptr; int64_t trmm_nheavy = 0;
-  int32_t* trmm_items[2] = {nullptr, nullptr}; int64_t trmm_nitems[2][2] = {{0, 0}, {0, 0}};
-  int32_t* trmm_tiles[2] = {nullptr, nullptr}; int64_t trmm_ntiles[2][2] = {{0, 0}, {0, 0}};
-  // rank-k updates on the pattern (front_syr2k.hip): (clique, row chunk, column chunk, zero) items of the FMA kernel, those of
-  // the large fronts LAST ([0]: items without them, [1]: all), and (clique, row tile, column tile, zero) tiles of the tile
-  // products, those of the large fronts FIRST ([0]: theirs, [1]: all); zero: all rows above the diagonal, only zeros are stored
-  int32_t* syr2k_items = nullptr; int64_t syr2k_nitems[2] = {0, 0};
-  int32_t* syr2k_tiles = nullptr; int64_t syr2k_ntiles[2] = {0, 0};
-  bool syr2k_ready = false;
-  // products of the matrix itself (front_symm.hip): the contribution index (row i of C owns the positions [symm_tptr[i],
-  // symm_tptr[i + 1]) of the list of all symm_ntot partials; symm_pos: per item the positions of its row partials, then of its
-  // column partials), the rows with more than SYMM_HEAVY partials, and the (clique, row chunk, column part, base in symm_pos)
-  // items, those of the large fronts FIRST ([0]: theirs, [1]: all).  symm_ntot: -1 until counted (csp_symm_positions: host only)
-  int64_t* symm_tptr = nullptr; int32_t* symm_pos = nullptr;
-  int32_t* symm_heavy = nullptr; int64_t symm_nheavy = 0;
-  int32_t* symm_items = nullptr; int64_t symm_nitems[2] = {0, 0};
-  int64_t symm_ntot = -1;
+  CompletionWs mrc;
+  PsdPlan psd;
+  TrmmPlan trmm;
+  Syr2kPlan syr2k;
+  SymmPlan symm;
   int64_t bytes = 0;
 };
 

@@ -13,7 +13,7 @@
 //   a COLUMN partial for each column kk < last of its part:  sum over the rows m > kk of the chunk of P[m, kk] B[F_m, :],
 //     target row N_kk of C.
 // Every partial has one position in a list of ntot: row i of C owns the positions [tptr[i], tptr[i + 1]), its partials in
-// ascending (k, side, r, p), side 0 = row partial, 1 = column partial (capi.hip: symm_index; specified by the numpy
+// ascending (k, side, r, p), side 0 = row partial, 1 = column partial (products.hip: symm_setup; specified by the numpy
 // restatement of tests/symm_ref.py).  Phase 1 stores the value of the partial at position q for column c at U[q + c ntot]
 // in the update workspace, so phase 2 reads no index but tptr:
 //   C[i, c] = beta C[i, c] + alpha (the run of row i summed in ascending position),

@@ -9,7 +9,7 @@
 //     T:  X_N = L_NN^T B_N + L_AN^T B[A]                 -> X (a pure gather through rowidx)
 //   phase 2, combine:
 //     N:  B[i, c] = alpha (X[i, c] + sum U_k[q, c]) over the separator entries (k, q) with rowidx = i, in ascending k.  The
-//         host lays the transposed separator index out once per context (capi.hip: trmm_setup): row i owns the positions
+//         host lays the transposed separator index out once per context (products.hip: trmm_setup): row i owns the positions
 //         [tptr[i], tptr[i + 1]) of a list of all ntot = sepptr[nsn] separator entries, its own in ascending k, and
 //         pos[sepptr[k] + q] is the position of entry (k, q).  Phase 1 stores U_k through pos, so the contributions to one
 //         entry of B are CONTIGUOUS in the workspace, already in the order of the sum: the combine pass reads no index but

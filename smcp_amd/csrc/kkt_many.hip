@@ -240,12 +240,7 @@ int potrs_many_impl(csp_ctx* c, const double* A, int64_t n, int64_t lda, double*
     return 0;
   }
   // the forward solution lives in the scratch image of csp_trsm / csp_trmm (no call keeps it): n x nrhs, leading dimension n
-  const int64_t need = n * nrhs;
-  if (D.trsm_x_len < need) {
-    if (D.trsm_x) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(D.trsm_x)); D.bytes -= D.trsm_x_len * 8; D.trsm_x = nullptr; D.trsm_x_len = 0; }
-    if (int rc = dev_alloc(&D.trsm_x, need, D.bytes)) return rc;
-    D.trsm_x_len = need;
-  }
+  if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, n * nrhs, D.bytes, st)) return rc;
   double* const Yw = D.trsm_x;
   // the updates of the other rows: FMA below eight columns of a workgroup's block, tile products on the matrix cores from eight on
   // (the gate of csp_trmm / csp_symm); SMCP_POTRS_MANY_MM=0: FMA only.  Read on every call: tools/solve_many_time.py alternates the two

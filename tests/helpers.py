@@ -1,4 +1,6 @@
 """Shared test utilities: patterns, dense references (numpy), oracle wiring."""
+import ctypes
+
 import numpy as np
 
 from oracle import oracle as orc
@@ -84,3 +86,64 @@ def random_spd_on_V(S, seed=0):
 
 def proj(S, M):
     return np.where(S.mask(), M, 0.0)
+
+
+# ---- shared by the tests of the dense-block products and the completions ---------------------------------------------
+def two_components():
+    """a band and a block arrow that share nothing"""
+    band = [(np.array([j]), np.arange(j, min(20, j + 4))) for j in range(20)]
+    arrow = [(np.arange(20 + 5 * b, 25 + 5 * b), np.concatenate([np.arange(20 + 5 * b, 25 + 5 * b), np.arange(35, 41)])) for b in range(3)]
+    arrow.append((np.arange(35, 41), np.arange(35, 41)))
+    return problems._from_cliques(41, band + arrow)
+
+
+EXTRA = {"two_components": two_components, "one_clique": lambda: problems.band_pattern(33, 32),
+         "wide_arrow": lambda: problems.block_arrow_pattern(150, 2, 6)}
+
+SYMB = {}
+
+
+def symb_of(name):
+    """the Symbolic of a pattern of GPU_PATTERNS (host only), built once"""
+    if name not in SYMB:
+        SYMB[name] = Symbolic(GPU_PATTERNS[name]())
+    return SYMB[name]
+
+
+def padded(M, pad, fill=7.25):
+    """the (k, n) device view of an n x k numpy block inside a tensor with `pad` padding columns, and that tensor"""
+    import torch
+    n, k = M.shape
+    full = torch.full((k, n + pad), fill, dtype=torch.float64, device="cuda")
+    view = full[:, :n]
+    view.copy_(torch.from_numpy(np.ascontiguousarray(M.T)))
+    return view, full
+
+
+def random_block(n, k, pad, seed):
+    """(n x k numpy block, its (k, n) device view, the padded tensor behind the view)"""
+    B = np.random.default_rng(seed).standard_normal((n, k))
+    view, full = padded(B, pad)
+    return B, view, full
+
+
+def launch_counts(symb, fn):
+    """kernel name -> launches while fn() runs (csp_profile_*: every launch of the library is counted)"""
+    import torch
+    from smcp_amd import _lib
+    lib = _lib.lib()
+    h = symb.handle
+    nk = int(lib.csp_profile_kinds())
+    names = [lib.csp_profile_kernel_name(i).decode() for i in range(nk)]
+    lib.csp_profile_filter(h, -1)
+    lib.csp_profile_enable(h, 1)
+    lib.csp_profile_read(h, None, None)
+    try:
+        fn()
+        torch.cuda.synchronize()
+        ms = (ctypes.c_double * nk)()
+        cnt = (ctypes.c_int64 * nk)()
+        lib.csp_profile_read(h, ms, cnt)
+    finally:
+        lib.csp_profile_enable(h, 0)
+    return {names[i]: int(cnt[i]) for i in range(nk) if cnt[i]}

@@ -81,8 +81,8 @@ def items_of(symb, rows=64, kp=256):
 def contribution_index(symb, rows=64, kp=256):
     """(tptr, rec): rec is an (ntot, 5) array whose row q = (k, side, r, p, j) names the partial at position q: side 0 the
     row partial of row rows * r + j of item (k, r, p), side 1 the column partial of its column kp * p + j.  Row i of the
-    matrix owns the positions tptr[i] : tptr[i + 1], in ascending (k, side, r, p).  The device's index (capi.hip:
-    symm_index) is specified by this one; csp_symm_positions returns len(rec)."""
+    matrix owns the positions tptr[i] : tptr[i + 1], in ascending (k, side, r, p).  The device's index (products.hip:
+    symm_setup) is specified by this one; csp_symm_positions returns len(rec)."""
     snptr, rowptr, rowidx = symb.snptr, symb.rowptr, symb.rowidx
     tgt, rec = [], []
     for k, r, p, nrows, ncol in items_of(symb, rows, kp):

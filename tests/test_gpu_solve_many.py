@@ -12,9 +12,8 @@ from smcp_amd import _lib, chordal, problems, shard
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.kkt import KKTSystem, solve_many_chunks
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import GPU_PATTERNS
+from tests.helpers import GPU_PATTERNS, launch_counts
 from tests.test_gpu_parity import dev, host, rel, setup
-from tests.test_gpu_trmm import launch_counts
 
 pytestmark = pytest.mark.gpu
 

@@ -10,9 +10,8 @@ import torch
 from smcp_amd import _lib, chordal
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import GPU_PATTERNS
+from tests.helpers import EXTRA, GPU_PATTERNS, launch_counts, padded
 from tests.symm_ref import EPS, composed_bound, contribution_index, dense_symm, matrix_input, symm_bound
-from tests.test_gpu_trmm import EXTRA, launch_counts
 from tests.trmm_ref import factor_input
 
 pytestmark = pytest.mark.gpu
@@ -38,15 +37,6 @@ def case(name):
     if name not in CASES:
         CASES[name] = Case(name)
     return CASES[name]
-
-
-def padded(M, pad, fill=7.25):
-    """the (k, n) device view of an n x k numpy block inside a tensor with `pad` padding columns, and that tensor"""
-    n, k = M.shape
-    full = torch.full((k, n + pad), fill, dtype=torch.float64, device="cuda")
-    view = full[:, :n]
-    view.copy_(torch.from_numpy(np.ascontiguousarray(M.T)))
-    return view, full
 
 
 def device_symm(name, B, C, padb, padc, alpha, beta):

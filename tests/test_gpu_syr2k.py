@@ -12,7 +12,8 @@ import torch
 from smcp_amd import _lib, chordal, problems
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import GPU_PATTERNS, PATTERNS
+from tests import helpers
+from tests.helpers import GPU_PATTERNS, PATTERNS, launch_counts, random_block
 from tests.syr2k_ref import EPS, dense_syr2k, lower_index, matrix_input, owned, pattern_mask, syr2k_bound
 from tests.test_mrcompletion_host import low_rank_on_V, mrcompletion as mrc_numpy, pd_on_V
 
@@ -24,15 +25,7 @@ FORMS = ("syr2k", "syrk", "alias")
 CASES = {}
 
 
-def two_components():
-    """a band and a block arrow that share nothing"""
-    band = [(np.array([j]), np.arange(j, min(20, j + 4))) for j in range(20)]
-    arrow = [(np.arange(20 + 5 * b, 25 + 5 * b), np.concatenate([np.arange(20 + 5 * b, 25 + 5 * b), np.arange(35, 41)])) for b in range(3)]
-    arrow.append((np.arange(35, 41), np.arange(35, 41)))
-    return problems._from_cliques(41, band + arrow)
-
-
-EXTRA = {"two_components": two_components, "one_clique": lambda: problems.band_pattern(33, 32)}
+EXTRA = {name: helpers.EXTRA[name] for name in ("two_components", "one_clique")}
 
 
 class Case:
@@ -54,15 +47,6 @@ def case(name):
     if name not in CASES:
         CASES[name] = Case(name)
     return CASES[name]
-
-
-def block(n, k, pad, seed):
-    """(n x k numpy block, its (k, n) device view, the padded tensor behind the view)"""
-    B = np.random.default_rng(seed).standard_normal((n, k))
-    full = torch.full((k, n + pad), 7.25, dtype=torch.float64, device="cuda")
-    view = full[:, :n]
-    view.copy_(torch.from_numpy(np.ascontiguousarray(B.T)))
-    return B, view, full
 
 
 def call(X, form, Uv, Vv, alpha, beta):
@@ -104,8 +88,8 @@ def check_definition(name, ranks=RANKS):
             for alpha, beta in AB:
                 pad = 3 * (combo % 2)                                # ldu = ldv = n on one half of the cases, n + 3 on the other
                 combo += 1
-                U, Uv, Ufull = block(n, k, pad, 100 + combo)
-                V, Vv, Vfull = block(n, k, pad, 500 + combo)
+                U, Uv, Ufull = random_block(n, k, pad, 100 + combo)
+                V, Vv, Vfull = random_block(n, k, pad, 500 + combo)
                 got = device_update(cs, form, Uv, Ufull, Vv, Vfull, alpha, beta)
                 Vr = None if form == "syrk" else (U if form == "alias" else V)
                 ref = dense_syr2k(cs.Xd, cs.mask, U, Vr, alpha, beta)
@@ -138,26 +122,6 @@ def test_generic_route(name):
         chordal.tune(symb, chordal.TUNE_DETERMINISTIC, 0)
 
 
-def launch_counts(symb, fn):
-    """kernel name -> launches while fn() runs (csp_profile_*: every launch of the library is counted)"""
-    lib = _lib.lib()
-    h = symb.handle
-    nk = int(lib.csp_profile_kinds())
-    names = [lib.csp_profile_kernel_name(i).decode() for i in range(nk)]
-    lib.csp_profile_filter(h, -1)
-    lib.csp_profile_enable(h, 1)
-    lib.csp_profile_read(h, None, None)
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms = (ctypes.c_double * nk)()
-        cnt = (ctypes.c_int64 * nk)()
-        lib.csp_profile_read(h, ms, cnt)
-    finally:
-        lib.csp_profile_enable(h, 0)
-    return {names[i]: int(cnt[i]) for i in range(nk) if cnt[i]}
-
-
 def test_launch_count_does_not_depend_on_the_tree():
     """band has 27 levels, rand2 7, nested_mid 4: a call is at most two launches on each; one FMA launch at k = 1."""
     levels = {}
@@ -166,8 +130,8 @@ def test_launch_count_does_not_depend_on_the_tree():
         symb = cs.symb
         levels[name] = symb.nlev
         for k in (1, 8, 70):
-            _, Uv, _ = block(symb.n, k, 0, 9)
-            _, Vv, _ = block(symb.n, k, 0, 10)
+            _, Uv, _ = random_block(symb.n, k, 0, 9)
+            _, Vv, _ = random_block(symb.n, k, 0, 10)
             X = cspmatrix(symb, cs.blk_d.clone())
             for form in FORMS:
                 call(X, form, Uv, Vv, 0.5, 0.5)                      # (the lists are built outside the count)
@@ -184,8 +148,8 @@ def test_launch_count_does_not_depend_on_the_tree():
 def test_syr2_is_syr2k_with_one_rank(name):
     cs = case(name)
     n = cs.symb.n
-    _, Uv, _ = block(n, 1, 0, 11)
-    _, Vv, _ = block(n, 1, 0, 12)
+    _, Uv, _ = random_block(n, 1, 0, 11)
+    _, Vv, _ = random_block(n, 1, 0, 12)
     A = cspmatrix(cs.symb, cs.blk_d.clone())
     B = cspmatrix(cs.symb, cs.blk_d.clone())
     chordal.syr2(A, Uv[0], Vv[0], -0.5, 2.0)
@@ -201,8 +165,8 @@ def test_adjoint_identity_with_trmm(name, k):
     cs = case(name)
     symb, n = cs.symb, cs.symb.n
     W = cspmatrix(symb, torch.from_numpy(np.nan_to_num(cs.blk, nan=0.0)).cuda())
-    U, Uv, _ = block(n, k, 0, 21)
-    V, Vv, _ = block(n, k, 3, 22)
+    U, Uv, _ = random_block(n, k, 0, 21)
+    V, Vv, _ = random_block(n, k, 3, 22)
     Z = cspmatrix(symb, torch.full_like(cs.blk_d, float("nan")))
     chordal.syr2k(Z, Uv, Vv, 1.0, 0.0)
     lhs = chordal.dot(W, Z)

@@ -12,25 +12,13 @@ import torch
 from smcp_amd import _lib, chordal, problems
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import GPU_PATTERNS
+from tests.helpers import EXTRA, GPU_PATTERNS, launch_counts, random_block
 from tests.trmm_ref import U, dense_trmm, factor_input, product_bound, transposed_separator_index
 
 pytestmark = pytest.mark.gpu
 
 NRHS = (1, 7, 8, 17, 70)       # below, at and above the tile gate; one past a 16-column block; two 64-column tiles, the second ragged
 CASES = {}
-
-
-def two_components():
-    """a band and a block arrow that share nothing"""
-    band = [(np.array([j]), np.arange(j, min(20, j + 4))) for j in range(20)]
-    arrow = [(np.arange(20 + 5 * b, 25 + 5 * b), np.concatenate([np.arange(20 + 5 * b, 25 + 5 * b), np.arange(35, 41)])) for b in range(3)]
-    arrow.append((np.arange(35, 41), np.arange(35, 41)))
-    return problems._from_cliques(41, band + arrow)
-
-
-EXTRA = {"two_components": two_components, "one_clique": lambda: problems.band_pattern(33, 32),
-         "wide_arrow": lambda: problems.block_arrow_pattern(150, 2, 6)}
 
 
 def case(name):
@@ -43,15 +31,6 @@ def case(name):
         Lz = cspmatrix(symb, torch.from_numpy(np.nan_to_num(blk, nan=0.0)).cuda())
         CASES[name] = (symb, L, Lz, Ld)
     return CASES[name]
-
-
-def rhs(n, nrhs, pad, seed):
-    """(B as n x nrhs numpy, the (nrhs, n) device view of a tensor with `pad` padding columns, that tensor)"""
-    B = np.random.default_rng(seed).standard_normal((n, nrhs))
-    full = torch.full((nrhs, n + pad), 7.25, dtype=torch.float64, device="cuda")
-    view = full[:, :n]
-    view.copy_(torch.from_numpy(np.ascontiguousarray(B.T)))
-    return B, view, full
 
 
 def device_trmm(name, B, pad, alpha, trans):
@@ -112,26 +91,6 @@ def test_generic_route(name):
         chordal.tune(symb, chordal.TUNE_DETERMINISTIC, 0)
 
 
-def launch_counts(symb, fn):
-    """kernel name -> launches while fn() runs (csp_profile_*: every launch of the library is counted)"""
-    lib = _lib.lib()
-    h = symb.handle
-    nk = int(lib.csp_profile_kinds())
-    names = [lib.csp_profile_kernel_name(i).decode() for i in range(nk)]
-    lib.csp_profile_filter(h, -1)
-    lib.csp_profile_enable(h, 1)
-    lib.csp_profile_read(h, None, None)
-    try:
-        fn()
-        torch.cuda.synchronize()
-        ms = (ctypes.c_double * nk)()
-        cnt = (ctypes.c_int64 * nk)()
-        lib.csp_profile_read(h, ms, cnt)
-    finally:
-        lib.csp_profile_enable(h, 0)
-    return {names[i]: int(cnt[i]) for i in range(nk) if cnt[i]}
-
-
 def test_launch_count_does_not_depend_on_the_tree():
     """band has 27 levels, rand2 7, nested_mid 4: a call is at most four launches on each, and trees that take the same
     route (the same set of kernels: with or without tile products for large fronts) take the same number."""
@@ -142,7 +101,7 @@ def test_launch_count_does_not_depend_on_the_tree():
         levels[name] = symb.nlev
         for nrhs in (1, 70):
             for trans in ("N", "T"):
-                _, view, _ = rhs(symb.n, nrhs, 0, 9)
+                _, view, _ = random_block(symb.n, nrhs, 0, 9)
                 chordal.trmm(L, view, 1.0, trans)                    # (workspaces grown outside the count)
                 cnt = launch_counts(symb, lambda: chordal.trmm(L, view, 1.0, trans))
                 total = sum(cnt.values())
@@ -162,7 +121,7 @@ def test_round_trip_with_trsm(name):
     symb, L, Lz, Ld = case(name)
     for trans in (False, True):
         for nrhs in (4, 70):
-            B, view, _ = rhs(symb.n, nrhs, 0, 21 + nrhs)
+            B, view, _ = random_block(symb.n, nrhs, 0, 21 + nrhs)
             t = "T" if trans else "N"
             chordal.trmm(L, view, 1.0, t)
             chordal.trsm(Lz, view, t)
@@ -179,7 +138,7 @@ def test_round_trip_with_trsm(name):
 def test_composition_is_the_product_with_S(name):
     symb, L, _, Ld = case(name)
     for nrhs in (3, 20):
-        B, view, _ = rhs(symb.n, nrhs, 0, 31)
+        B, view, _ = random_block(symb.n, nrhs, 0, 31)
         chordal.trmm(L, view, 1.0, "T")
         chordal.trmm(L, view, 1.0, "N")
         got = view.cpu().numpy().T

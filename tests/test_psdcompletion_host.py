@@ -15,7 +15,7 @@ import pytest
 import scipy.linalg as sla
 
 import smcp_amd
-from helpers import GPU_PATTERNS
+from helpers import GPU_PATTERNS, symb_of
 from smcp_amd import _lib
 from smcp_amd.symbolic import Symbolic
 from test_mrcompletion_host import blkval_of, clique_rows, dense_of, pchol
@@ -161,15 +161,6 @@ def rel_err(A, B):
 
 
 NAMES = sorted(GPU_PATTERNS)
-SYMB = {}
-
-
-def symb_of(name):
-    if name not in SYMB:
-        SYMB[name] = Symbolic(GPU_PATTERNS[name]())
-    return SYMB[name]
-
-
 # ---- properties ------------------------------------------------------------------------------------------------------
 def test_pchol_pivots_is_pchol():
     rng = np.random.default_rng(0)

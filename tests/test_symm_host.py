@@ -10,17 +10,10 @@ import torch
 import smcp_amd
 from smcp_amd import _lib
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import GPU_PATTERNS, PATTERNS
+from tests.helpers import GPU_PATTERNS, PATTERNS, symb_of
 from tests.symm_ref import contribution_index, dense_symm, items_of, matrix_input, symm_bound, symm_two_phase
 
-SYMB = {}
 SETTINGS = [(64, 256), (4, 8)]     # the device's; and one at which patterns of at most 30 rows have several chunks, parts and skipped items
-
-
-def symb_of(name):
-    if name not in SYMB:
-        SYMB[name] = Symbolic(GPU_PATTERNS[name]())
-    return SYMB[name]
 
 
 @pytest.mark.parametrize("rows,kp", SETTINGS)

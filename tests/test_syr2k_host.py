@@ -11,18 +11,9 @@ import smcp_amd
 from smcp_amd import _lib
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import PATTERNS
+from tests.helpers import PATTERNS, symb_of
 from tests.syr2k_ref import (dense_syr2k, lower_index, matrix_input, owned, pattern_mask, syr2k_bound, syr2k_per_clique,
                              to_dense)
-
-SYMB = {}
-
-
-def symb_of(name):
-    if name not in SYMB:
-        SYMB[name] = Symbolic(PATTERNS[name]())
-    return SYMB[name]
-
 
 @pytest.mark.parametrize("k", [1, 3, 9])
 @pytest.mark.parametrize("ab", [(1.0, 0.0), (-0.5, 1.0), (2.0, -0.25)])

@@ -9,17 +9,8 @@ import torch
 import smcp_amd
 from smcp_amd import _lib
 from smcp_amd.symbolic import Symbolic
-from tests.helpers import PATTERNS
+from tests.helpers import PATTERNS, symb_of
 from tests.trmm_ref import dense_trmm, factor_input, product_bound, transposed_separator_index, trmm_two_phase
-
-SYMB = {}
-
-
-def symb_of(name):
-    if name not in SYMB:
-        SYMB[name] = Symbolic(PATTERNS[name]())
-    return SYMB[name]
-
 
 @pytest.mark.parametrize("name", sorted(PATTERNS))
 def test_transposed_separator_index(name):

@@ -46,7 +46,7 @@ def dense_trmm(Ld, B, alpha, trans):
 def transposed_separator_index(symb):
     """(tptr, tk, tq): row i of the matrix appears as separator entry q of clique k for the pairs
     (tk[p], tq[p]), p in [tptr[i], tptr[i + 1]), in ascending k.  Built from snptr / rowptr / rowidx / sepptr; the device's
-    index (capi.hip: trmm_setup) is specified by this one: it keeps tptr and, per separator entry, its position p here, and
+    index (products.hip: trmm_setup) is specified by this one: it keeps tptr and, per separator entry, its position p here, and
     stores U_k[q] at position p, so that the contributions to a row lie side by side in the order of the sum."""
     snptr, rowptr, rowidx, sepptr = symb.snptr, symb.rowptr, symb.rowidx, symb.sepptr
     rows, ks, qs = [], [], []
