@@ -97,7 +97,7 @@ int csp_index_map(const csp_ctx* ctx, int64_t cnt, const int64_t* I, const int64
  * grows the workspace.  One process drives ONE device: a different device for an initialised context, or for
  * another context of the same process, returns SMCP_EINVAL (one rank per GPU is the multi-GPU model). */
 int csp_device_init(csp_ctx* ctx, int device, int64_t max_rhs);
-/* Bytes of HBM held by the context (index arrays + workspaces). */
+/* Bytes of device memory this context holds now (index arrays, tables, workspaces, scratch). */
 int64_t csp_device_bytes(const csp_ctx* ctx);
 
 /* ---- chordal kernels (all in place, device pointers) ------------------------------- */

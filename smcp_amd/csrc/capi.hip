@@ -285,50 +285,6 @@ void run_threads(int nth, F work) {
   for (auto& th : pool) th.join();
 }
 
-template <class T>
-int dev_upload(T** dst, const std::vector<T>& src, int64_t& bytes) {
-  size_t n = std::max<size_t>(src.size(), 1) * sizeof(T);
-  if (hipMalloc((void**)dst, n) != hipSuccess) return SMCP_ENOMEM;
-  if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-    return SMCP_EHIP;
-  bytes += (int64_t)n;
-  return 0;
-}
-template <class T>
-int dev_alloc(T** dst, int64_t count, int64_t& bytes) {
-  size_t n = (size_t)std::max<int64_t>(count, 1) * sizeof(T);
-  // SMCP_CONTIG=1 (placement studies): large buffers from physically contiguous memory (hipDeviceMallocContiguous)
-  static int contig = -1;
-  if (contig < 0) { const char* e = sw_str("SMCP_CONTIG"); contig = (e && e[0] == '1') ? 1 : 0; }
-  hipError_t arc = hipErrorUnknown;
-  if (contig && n >= ((size_t)1 << 24)) arc = hipExtMallocWithFlags((void**)dst, n, hipDeviceMallocContiguous);
-  if (arc != hipSuccess) { (void)hipGetLastError(); arc = hipMalloc((void**)dst, n); }
-  if (arc != hipSuccess) return SMCP_ENOMEM;
-  bytes += (int64_t)n;
-  // SMCP_POISON=1 (hunting reads of never-written workspace): every fp64 buffer starts as 4.5e150 in every entry instead of
-  // whatever the previous owner of the memory left there -- which, in a re-run of the same test, is the same data at the same
-  // addresses and hides the read.  Index arrays are left alone (a poisoned index would fault, not mis-compute).
-  if (std::is_same<T, double>::value) {
-    static int poison = -1;
-    if (poison < 0) poison = sw_on("SMCP_POISON", 0);
-    if (poison && hipMemset((void*)*dst, 0x5F, n) != hipSuccess) return SMCP_EHIP;
-  }
-  { static int dbg = -1; if (dbg < 0) { const char* e = sw_str("SMCP_DEBUG_ADDR"); dbg = (e && e[0] == '1') ? 1 : 0; }      // placement studies
-    if (dbg && n >= ((size_t)1 << 24)) fprintf(stderr, "smcp_amd: alloc %zu MB at %p\n", n >> 20, (void*)*dst); }
-  return 0;
-}
-
-// Grows a scratch buffer that no call keeps to at least `need` elements; its contents are lost.  An older buffer is freed
-// only once the stream has drained: launches of earlier calls may still use it.
-template <class T>
-int dev_grow(T** buf, int64_t* len, int64_t need, int64_t& bytes, hipStream_t st) {
-  if (*len >= need) return 0;
-  if (*buf) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipFree(*buf)); bytes -= *len * (int64_t)sizeof(T); *buf = nullptr; *len = 0; }
-  if (int rc = dev_alloc(buf, need, bytes)) return rc;
-  *len = need;
-  return 0;
-}
-
 TreeArgs tree_args(csp_ctx* c) {
   TreeArgs a;
   a.cl = c->D.cl;
@@ -828,19 +784,18 @@ bool flow_chol(csp_ctx* c, hipStream_t st, double* A, int64_t ld, int n, double*
   csp_ctx::FlowWs& W = c->flow_ws[st == c->aux_stream[0] && st ? 1 : (st == c->aux_stream[1] && st ? 2 : 0)];
   if (W.cap_nt < nt || W.cap_fronts < cnt) {
     // (the buffers may be in use by a launch still queued on this stream: hipFree waits for the device)
+    // (all three lengths rise with either capacity, so all three buffers are replaced; fresh flags are zero and the epoch starts over)
     const int ntc = std::max(nt, W.cap_nt), ntilesc = ntc * (ntc + 1) / 2, frc = std::max(cnt, W.cap_fronts);
-    for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) (void)hipFree(q);
-    W = csp_ctx::FlowWs();
-    int64_t junk = 0;
-    if (dev_alloc(&W.P, (int64_t)frc * ntilesc * 4096, junk) || dev_alloc(&W.dinv, (int64_t)frc * ntc * 4096, junk) ||
-        hipMalloc((void**)&W.flags, sizeof(unsigned) * (size_t)frc * (size_t)(ntilesc + ntc + 4)) != hipSuccess ||
-        hipMemset(W.flags, 0, sizeof(unsigned) * (size_t)frc * (size_t)(ntilesc + ntc + 4)) != hipSuccess) {
+    DevLedger& mem = c->D.mem;
+    W.epoch = 0;
+    if (dev_grow(&W.P, &W.len_P, (int64_t)frc * ntilesc * 4096, mem, st) || dev_grow(&W.dinv, &W.len_dinv, (int64_t)frc * ntc * 4096, mem, st) ||
+        dev_grow(&W.flags, &W.len_flags, (int64_t)frc * (ntilesc + ntc + 4), mem, st) ||
+        hipMemset(W.flags, 0, sizeof(unsigned) * (size_t)W.len_flags) != hipSuccess) {
       (void)hipGetLastError();
-      for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) (void)hipFree(q);
+      (void)dev_free(mem, W.P, W.dinv, W.flags);
       W = csp_ctx::FlowWs();
       return false;
     }
-    c->D.bytes += junk + (int64_t)sizeof(unsigned) * frc * (ntilesc + ntc + 4);
     W.cap_nt = ntc; W.cap_fronts = frc;
   }
   const int wgs_front = cnt > 1 ? wgs / cnt : (n > 2048 ? (wgs * 10) / 7 : wgs);
@@ -854,9 +809,11 @@ bool flow_chol(csp_ctx* c, hipStream_t st, double* A, int64_t ld, int n, double*
     flow_make_plan(n, wgs_front, optr, otile);
     csp_ctx::FlowPlanDev P;
     P.nwg = (int)optr.size() - 1;
-    int64_t junk = 0;
-    if (dev_upload(&P.own_ptr, optr, junk) || dev_upload(&P.own_tile, otile, junk)) { (void)hipGetLastError(); return false; }
-    c->D.bytes += junk;
+    if (dev_upload(&P.own_ptr, optr, c->D.mem) || dev_upload(&P.own_tile, otile, c->D.mem)) {
+      (void)hipGetLastError();
+      (void)dev_free(c->D.mem, P.own_ptr, P.own_tile);
+      return false;
+    }
     it = c->flow_plans.emplace(plan_key, P).first;
   }
   FlowArgs f;
@@ -1201,12 +1158,7 @@ bool launch_fam2(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, in
     attr = true;
   }
   const int64_t need = (int64_t)cnt * fam2_const_doubles(cnn, csa);
-  if (D.famc_len < need) {
-    if (D.famc) { if (hipFree(D.famc) != hipSuccess) return false; D.bytes -= D.famc_len * 8; }
-    D.famc = nullptr; D.famc_len = 0;
-    if (dev_alloc(&D.famc, need, D.bytes)) return false;
-    D.famc_len = need;
-  }
+  if (dev_grow(&D.famc, &D.famc_len, need, D.mem, st)) return false;
   const int ncu = D.ncu;
   // one workgroup per CU (LDS), two right-hand sides in flight per workgroup: split the right-hand sides so that the
   // grid fills whole rounds; set-up ~ 4 passes
@@ -1298,12 +1250,7 @@ bool launch_famt(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, in
       attrg = ok;
     }
     const int64_t need = (int64_t)cnt * (FAMT_HDR + L.total);
-    if (ok && D.famc_len < need) {
-      if (D.famc) { if (hipFree(D.famc) != hipSuccess) ok = false; D.bytes -= D.famc_len * 8; }
-      D.famc = nullptr; D.famc_len = 0;
-      if (ok && dev_alloc(&D.famc, need, D.bytes)) ok = false;
-      if (ok) D.famc_len = need;
-    }
+    if (ok && dev_grow(&D.famc, &D.famc_len, need, D.mem, st)) ok = false;
     if (!ok) {
       fprintf(stderr, "smcp_amd: grouped family sweep not launchable\n");
       if (!c->launch_err) c->launch_err = -1;
@@ -1332,12 +1279,7 @@ bool launch_famt(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, in
     attr = true;
   }
   const int64_t need = (int64_t)cnt * (FAMT_HDR + L.total);
-  if (D.famc_len < need) {
-    if (D.famc) { if (hipFree(D.famc) != hipSuccess) return false; D.bytes -= D.famc_len * 8; }
-    D.famc = nullptr; D.famc_len = 0;
-    if (dev_alloc(&D.famc, need, D.bytes)) return false;
-    D.famc_len = need;
-  }
+  if (dev_grow(&D.famc, &D.famc_len, need, D.mem, st)) return false;
   const int ncu = D.ncu;
   // one workgroup per CU (LDS), eight right-hand sides in flight per workgroup: split the right-hand sides so that the
   // grid fills whole rounds; the set-up (tables, entry lists) costs about as much as four passes (half a round of eight: since
@@ -1429,8 +1371,8 @@ bool try_lfsp(csp_ctx* c, const MfmaArgs& a, int cnt, int nrhs, double* U, int64
   if (D.kc_maxlist_large <= 0 || D.kc_maxlist_large > LFSP_ECAP || !D.lfsp_cnt) return false;
   const bool exact = D.lfsp_exact;      // every such front is exactly (64, 128): no bounds checks in the kernel
   if (!D.sp_rt) {
-    if (dev_alloc(&D.sp_rt, std::max<int64_t>(c->S.updlen(), 1), D.bytes)) return false;
-    if (dev_alloc(&D.sp_mk, std::max<int64_t>(c->S.blklen(), 1), D.bytes)) return false;
+    if (dev_alloc(&D.sp_rt, std::max<int64_t>(c->S.updlen(), 1), D.mem)) return false;
+    if (dev_alloc(&D.sp_mk, std::max<int64_t>(c->S.blklen(), 1), D.mem)) return false;
   }
   MfmaArgs b = a;
   b.sp_rt = D.sp_rt; b.sp_mk = D.sp_mk;
@@ -2080,125 +2022,6 @@ int hessian_impl(csp_ctx* c, const double* L, double* U, int64_t nrhs, int64_t l
 }
 
 
-bool fam_off() {
-  static int off = -1;
-  if (off < 0) { const char* e = sw_str("SMCP_FAM"); off = (e && e[0] == '0') ? 1 : 0; }
-  return off == 1;
-}
-// dynamic LDS of the family kernel instantiation that serves (parent separator famna, child separator famcna)
-size_t fam_bytes_for(int famna, int famcna, int fampan, int fampk) {
-  const int nat = std::max(1, (famna + 15) / 16), natc = std::max(1, (famcna + 15) / 16);
-  switch (nat * 2 + natc - 1) {
-    case 2: return fam_lds_bytes<1, 1>(fampan, fampk);
-    case 3: return fam_lds_bytes<1, 2>(fampan, fampk);
-    case 4: return fam_lds_bytes<2, 1>(fampan, fampk);
-    case 5: return fam_lds_bytes<2, 2>(fampan, fampk);
-    case 6: return fam_lds_bytes<3, 1>(fampan, fampk);
-    case 7: return fam_lds_bytes<3, 2>(fampan, fampk);
-    case 8: return fam_lds_bytes<4, 1>(fampan, fampk);
-    case 9: return fam_lds_bytes<4, 2>(fampan, fampk);
-  }
-  return (size_t)1 << 30;
-}
-
-// Splits the cliques selected by `keep` into per-level lists (LDS-class first -- its family tail last --, large
-// fronts after) and records the sizing maxima of each class.  lev2 is the concatenation of the lists, off[l] its start.
-template <class Keep>
-void classify_levels(const Symbolic& S, Keep keep, std::vector<LevelClass>& lvl, std::vector<int32_t>& lev2,
-                     std::vector<int64_t>& off) {
-  lvl.assign(S.nlev, LevelClass());
-  lev2.clear();
-  off.assign(S.nlev + 1, 0);
-  auto fits = [&](int64_t k) { return (size_t)mfma_lds_doubles((int)S.nn(k), (int)S.na(k)) * sizeof(double) <= LDS_LIMIT; };
-  // pass 1: sizing of the LDS class of every level; the joint maxima may not fit even if every clique does: the
-  // level's LDS class is demoted to the large-front class then
-  std::vector<uint8_t> demoted(S.nlev, 0);
-  for (int64_t l = 0; l < S.nlev; ++l) {
-    int nnm = 0, nam = 0;
-    bool any = false;
-    for (int64_t q = S.levptr[l]; q < S.levptr[l + 1]; ++q) {
-      const int64_t k = S.levidx[q];
-      if (!keep(k) || !fits(k)) continue;
-      any = true;
-      nnm = std::max<int>(nnm, (int)S.nn(k));
-      nam = std::max<int>(nam, (int)S.na(k));
-    }
-    if (any && (size_t)mfma_lds_doubles(nnm, nam) * sizeof(double) > LDS_LIMIT) demoted[l] = 1;
-  }
-  auto small = [&](int64_t k) { return fits(k) && !demoted[S.level[k]]; };
-  // pass 2: families.  Parent: small front, nn <= 16, na <= 64, 1..8 children, every child kept, childless, small,
-  // nn <= 16, na <= 32; all candidates of a level or none (one launch geometry per level).
-  std::vector<uint8_t> special(S.nsn, 0);
-  if (!fam_off())
-    for (int64_t l = 1; l < S.nlev; ++l) {
-      std::vector<int64_t> cand;
-      int famna = 0, fampan = 0, fampk = 0, famcna = 0, famnn = 0, famcnn = 0;
-      for (int64_t q = S.levptr[l]; q < S.levptr[l + 1]; ++q) {
-        const int64_t k = S.levidx[q];
-        if (!keep(k) || !small(k) || S.nn(k) > 16 || S.na(k) > 64) continue;
-        const int64_t nch = S.chptr[k + 1] - S.chptr[k];
-        if (nch < 1 || nch > 8) continue;
-        bool ok = true;
-        int cna = 0, cnn = 0;
-        for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1] && ok; ++q2) {
-          const int64_t ch = S.chidx[q2];
-          ok = keep(ch) && S.chptr[ch + 1] == S.chptr[ch] && small(ch) && S.nn(ch) <= 16 && S.na(ch) <= 32 && S.na(ch) >= 1;
-          cna = std::max<int>(cna, (int)S.na(ch));
-          cnn = std::max<int>(cnn, (int)S.nn(ch));
-        }
-        if (!ok) continue;
-        cand.push_back(k);
-        famnn = std::max<int>(famnn, (int)S.nn(k));
-        famcnn = std::max(famcnn, cnn);
-        famna = std::max<int>(famna, (int)S.na(k));
-        fampan = std::max<int>(fampan, (int)(S.nf(k) * S.nn(k)));
-        fampk = std::max<int>(fampk, (int)(S.na(k) * (S.na(k) + 1) / 2));
-        famcna = std::max(famcna, cna);
-      }
-      if (cand.empty() || fam_bytes_for(famna, famcna, fampan, fampk) > LDS_LIMIT) continue;
-      LevelClass& L = lvl[l];
-      L.famna = famna; L.fampan = fampan; L.fampk = fampk; L.famcna = famcna; L.famnn = famnn; L.famcnn = famcnn;
-      for (int64_t k : cand) {
-        special[k] = 1;
-        for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) special[S.chidx[q2]] = 1;
-      }
-    }
-  // pass 3: the lists
-  for (int64_t l = 0; l < S.nlev; ++l) {
-    LevelClass& L = lvl[l];
-    off[l] = (int64_t)lev2.size();
-    int64_t b = S.levptr[l], e = S.levptr[l + 1];
-    for (int pass = 0; pass < 3; ++pass)
-      for (int64_t q = b; q < e; ++q) {
-        int64_t k = S.levidx[q];
-        if (!keep(k)) continue;
-        const bool sm = small(k);
-        const int cls = sm ? (special[k] ? 1 : 0) : 2;
-        if (cls != pass) continue;
-        lev2.push_back((int32_t)k);
-        if (sm) {
-          L.nI++;
-          if (special[k]) L.nS++;
-          L.nnmaxI = std::max<int>(L.nnmaxI, (int)S.nn(k));
-          L.namaxI = std::max<int>(L.namaxI, (int)S.na(k));
-          int64_t rs = 0;
-          for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) rs += S.na(S.chidx[q2]) * (S.na(S.chidx[q2]) + 1) / 2;
-          L.plansumI = (int)std::max<int64_t>(L.plansumI, rs);
-          L.nchmaxI = std::max<int>(L.nchmaxI, (int)(S.chptr[k + 1] - S.chptr[k]));
-          L.panmaxI = std::max<int>(L.panmaxI, (int)(S.nf(k) * S.nn(k)));
-          L.pkmaxI = std::max<int>(L.pkmaxI, (int)(S.na(k) * (S.na(k) + 1) / 2));
-        } else {
-          L.nII++;
-          L.nnmaxII = std::max<int>(L.nnmaxII, (int)S.nn(k));
-          L.nnminII = std::min<int>(L.nnminII, (int)S.nn(k));
-          L.namaxII = std::max<int>(L.namaxII, (int)S.na(k));
-          L.nchmaxII = std::max<int>(L.nchmaxII, (int)(S.chptr[k + 1] - S.chptr[k]));
-        }
-      }
-  }
-  off[S.nlev] = (int64_t)lev2.size();
-}
-
 }  // namespace
 
 extern "C" {
@@ -2297,34 +2120,6 @@ int csp_status(csp_ctx* c, void* stream) {
   return v;
 }
 
-void csp_symbolic_destroy(csp_ctx* c) {
-  if (!c) return;
-  DeviceCtx& D = c->D;
-  if (D.device >= 0) {
-    hipSetDevice(D.device);
-    void* ptrs[] = {D.lfsp_skip, D.famt_skip, D.both_skip, D.trsm_x, D.fp, D.fp_bad, D.gsl_start, D.gsl_len, D.lg_list, D.lg_slot, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.sp_rt, D.sp_mk, D.lfsp_list, D.faci, D.lfd, D.lev3idx, D.updp, D.gp_tptr, D.gp_tgt, D.gp_cptr, D.gp_src, D.sw, D.gpart, D.lev2idx, D.lk, D.cl, D.rowidx, D.relidx, D.chidx, D.levidx, D.upd, D.yaa, D.fac, D.tmp, D.tmpptr,
-                    D.red, D.info, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack, D.qr_ws,
-                    D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.hinv, D.kc_ij, D.famc, D.scm_owner};
-    if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
-    D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
-    for (auto& W : c->flow_ws) for (void* q : {(void*)W.P, (void*)W.dinv, (void*)W.flags}) if (q) hipFree(q);
-    for (auto& kv : c->flow_plans) { if (kv.second.own_ptr) hipFree(kv.second.own_ptr); if (kv.second.own_tile) hipFree(kv.second.own_tile); }
-    for (void* p : ptrs) if (p) hipFree(p);
-    D.mrc.release(); D.psd.release(); D.trmm.release(); D.syr2k.release(); D.symm.release();
-    for (auto& G : c->lfsp_grp) { if (G.ptr) hipFree(G.ptr); if (G.list) hipFree(G.list); }
-    for (auto& G : c->famt_grp) { if (G.ptr) hipFree(G.ptr); if (G.list) hipFree(G.list); }
-    for (int q = 0; q < 2; ++q) {
-      if (c->aux_stream[q]) { (void)hipStreamSynchronize(c->aux_stream[q]); (void)hipStreamDestroy(c->aux_stream[q]); }
-      if (c->aux_join[q]) (void)hipEventDestroy(c->aux_join[q]);
-    }
-    if (c->aux_fork) (void)hipEventDestroy(c->aux_fork);
-    for (int set = 1; set <= 2; ++set) if (c->sets[set].lev2) hipFree(c->sets[set].lev2);
-    for (void* p : {(void*)c->xr_roots, (void*)c->xr_owner, (void*)c->xr_bptr}) if (p) hipFree(p);
-    if (D.info_host) hipHostFree(D.info_host);
-  }
-  delete c;
-}
-
 int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
   if (!c) return SMCP_EINVAL;
   const Symbolic& S = c->S;
@@ -2383,415 +2178,13 @@ int csp_index_map(const csp_ctx* c, int64_t cnt, const int64_t* I, const int64_t
   return 0;
 }
 
-// copies 1 .. K-1 of the extend-add gather plan of a K-fold replicated pattern: targets repeat, sources shift by the
-// packed update length of one copy, the source ranges by the source count of one copy
-__global__ void k_replicate_plan(int32_t* tgt, int64_t* cptr, int32_t* src, int64_t nt1, int64_t ns1, int64_t up1, int64_t K) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x, g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t e = g; e < nt1 * (K - 1); e += stride) {
-    const int64_t t = 1 + e / nt1, q = e % nt1;
-    tgt[t * nt1 + q] = tgt[q];
-    cptr[t * nt1 + q + 1] = cptr[q + 1] + t * ns1;
-  }
-  for (int64_t e = g; e < ns1 * (K - 1); e += stride) {
-    const int64_t t = 1 + e / ns1, q = e % ns1;
-    src[t * ns1 + q] = (int32_t)(src[q] + t * up1);
-  }
-}
+}  // extern "C"
 
-int csp_device_init(csp_ctx* c, int device, int64_t max_rhs) {
-  if (!c || max_rhs < 1) return SMCP_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return SMCP_ENODEV;
-  if (device < 0 || device >= ndev) return SMCP_EINVAL;
-  DeviceCtx& D = c->D;
-  const Symbolic& S = c->S;
-  if (D.device == device && D.max_rhs >= max_rhs) return 0;
-  // One process drives one GPU (one rank per GPU under torch.distributed): the launch helpers cache function
-  // attributes, occupancy and the CU count per process, and a context's buffers live on the device it was
-  // first initialised on.  A second device -- for this context or for another one of this process -- is refused.
-  static int bound_device = -1;
-  if (D.device >= 0 && D.device != device) return SMCP_EINVAL;
-  if (bound_device >= 0 && bound_device != device) return SMCP_EINVAL;
-  bound_device = device;
-  HIPCHK(hipSetDevice(device));
-  SetupClock clk("csp_device_init");
-  if (D.device < 0) {
-    std::vector<CliqueDesc> cl(S.nsn);
-    for (int64_t k = 0; k < S.nsn; ++k) {
-      CliqueDesc& d = cl[k];
-      d.blk = S.blkptr[k];
-      d.upd = S.updptr[k];
-      d.updp = S.updpptr[k];
-      d.rows = S.rowptr[k];
-      d.rel = S.sepptr[k];
-      d.nn = (int32_t)S.nn(k);
-      d.na = (int32_t)S.na(k);
-      d.parent = (int32_t)S.snpar[k];
-      d.chbeg = (int32_t)S.chptr[k];
-      d.chend = (int32_t)S.chptr[k + 1];
-      d.first = (int32_t)S.snptr[k];
-      d.pad = -1;
-    }
-    std::vector<int32_t> ch(S.chidx.begin(), S.chidx.end()), lev(S.levidx.begin(), S.levidx.end());
-    c->h_tmpptr.resize(S.nsn + 1);
-    for (int64_t k = 0; k <= S.nsn; ++k) c->h_tmpptr[k] = 2 * S.blkptr[k] + 256 * k;
-    D.tmplen = 2 * S.blklen() + 256 * S.nsn;
-    std::vector<int32_t> lev2;
-    std::vector<int64_t> lev2off;
-    classify_levels(S, [](int64_t) { return true; }, c->lvl, lev2, lev2off);
-    int rc = 0;
-    {
-      // slots of the large fronts (per-front 64 x 64 scratch) and the flat list of LDS-class cliques
-      int32_t slot = 0;
-      std::vector<int32_t> lev3, large;
-      c->lev_namax.assign(S.nlev, 0);
-      c->fam.assign(S.nsn, 0);
-      for (int64_t l = 0; l < S.nlev; ++l) {
-        const LevelClass& L = c->lvl[l];
-        int64_t b = S.levptr[l];
-        for (int64_t q = L.nI - L.nS; q < L.nI; ++q) c->fam[lev2[b + q]] = l ? 2 : 1;
-        for (int64_t q = 0; q < L.nI; ++q) lev3.push_back(lev2[b + q]);
-        for (int64_t q = L.nI; q < L.nI + L.nII; ++q) { cl[lev2[b + q]].pad = slot++; large.push_back(lev2[b + q]); }
-        c->lev_namax[l] = std::max(L.namaxI, L.namaxII);
-        if (L.nII) { D.nnmaxII_all = std::max(D.nnmaxII_all, L.nnmaxII); D.namaxII_all = std::max(D.namaxII_all, L.namaxII); }
-      }
-      c->large_mask.assign((size_t)S.nsn, 0);
-      for (int32_t k : large) c->large_mask[(size_t)k] = 1;
-      D.nI_total = (int64_t)lev3.size();
-      D.nII_total = (int64_t)large.size();
-      {
-        std::vector<int32_t> sp;       // childless large fronts the sparse-input sweep can take (front_lfsp.hip)
-        for (int32_t k : large)
-          if (S.chptr[k + 1] == S.chptr[k] && S.nn(k) <= 64 && S.na(k) <= 128 && S.na(k) > 0) sp.push_back(k);
-        D.lfsp_cnt = (int64_t)sp.size();
-        D.lfsp_exact = !sp.empty();
-        for (int32_t k : sp) if (S.nn(k) != 64 || S.na(k) != 128) D.lfsp_exact = false;
-        if (!sp.empty() && (rc = dev_upload(&D.lfsp_list, sp, D.bytes))) return rc;
-      }
-      {
-        // sibling groups for the sparse-input sweep (front_lfsp.hip, k_lfsp_up<..., GRP>): members of a large-front class all
-        // of whose fronts that sweep can take (childless, nn <= 64, 0 < na <= 128), under one LARGE parent, with identical
-        // relative indices; at most eight per group, in list order.  SMCP_LFSP_GROUP=0: none.
-        const char* ge = sw_str("SMCP_LFSP_GROUP");
-        const bool gon = !(ge && ge[0] == '0');
-        std::vector<uint8_t> is_large((size_t)S.nsn, 0), skip((size_t)S.nsn, 0);
-        for (int32_t k : large) is_large[(size_t)k] = 1;
-        c->lfsp_grp.assign((size_t)S.nlev, csp_ctx::LfspGroups());
-        c->lfsp_any_groups = false;
-        for (int64_t l = 0; l < S.nlev && gon; ++l) {
-          const LevelClass& L = c->lvl[l];
-          if (!L.nII || L.nchmaxII != 0 || L.nnmaxII > 64 || L.namaxII > 128) continue;
-          const int64_t b = S.levptr[l] + L.nI;
-          bool ok = true;
-          for (int64_t q = 0; q < L.nII; ++q) ok = ok && S.na(lev2[b + q]) > 0;
-          if (!ok) continue;
-          std::vector<int32_t> gptr(1, 0), glist;
-          std::vector<uint8_t> taken((size_t)L.nII, 0);
-          bool shared = false;
-          // the members of the class by parent, in list order: a front is only ever compared with its own siblings
-          std::unordered_map<int64_t, std::vector<int64_t>> sibs;
-          for (int64_t q = 0; q < L.nII; ++q) sibs[S.snpar[lev2[b + q]]].push_back(q);
-          for (int64_t q = 0; q < L.nII; ++q) {
-            if (taken[(size_t)q]) continue;
-            const int32_t k = lev2[b + q];
-            taken[(size_t)q] = 1;
-            glist.push_back(k);
-            int size = 1;
-            const int64_t par = S.snpar[k];
-            if (par >= 0 && is_large[(size_t)par]) {
-              const std::vector<int64_t>& sb = sibs[par];
-              for (auto it = std::upper_bound(sb.begin(), sb.end(), q); it != sb.end() && size < 8; ++it) {
-                const int64_t q2 = *it;
-                const int32_t k2 = lev2[b + q2];
-                if (taken[(size_t)q2] || S.na(k2) != S.na(k)) continue;
-                if (!std::equal(S.relidx.begin() + S.sepptr[k], S.relidx.begin() + S.sepptr[k + 1], S.relidx.begin() + S.sepptr[k2])) continue;
-                taken[(size_t)q2] = 1;
-                glist.push_back(k2);
-                ++size;
-              }
-            }
-            gptr.push_back((int32_t)glist.size());
-            if (size > 1) shared = true;
-          }
-          if (!shared) continue;
-          const int ng = (int)gptr.size() - 1;
-          for (int g = 0; g < ng; ++g) {
-            const int sz = gptr[(size_t)g + 1] - gptr[(size_t)g];
-            for (int q = 0; q < sz; ++q)
-              if (q != g % sz) skip[(size_t)glist[(size_t)gptr[(size_t)g] + q]] = 1;
-          }
-          csp_ctx::LfspGroups& G = c->lfsp_grp[(size_t)l];
-          if ((rc = dev_upload(&G.ptr, gptr, D.bytes))) return rc;
-          if ((rc = dev_upload(&G.list, glist, D.bytes))) return rc;
-          G.ngroups = ng;
-          c->lfsp_any_groups = true;
-        }
-        if (c->lfsp_any_groups && (rc = dev_upload(&D.lfsp_skip, skip, D.bytes))) return rc;
-        // sibling groups of FAMILY PARENTS for the entry-driven family sweep (front_famt.hip, k_fam_terms_grp): family parents of a
-        // level under one LARGE front with identical relative indices, at most FAMT_GMAX per group, in list order; the lists
-        // hold positions in the level's family list (= record indices of k_famt_prep).  Every family parent of the level is in
-        // exactly one group (singletons included).  SMCP_FAMT_GROUP=0: none.
-        const char* fe = sw_str("SMCP_FAMT_GROUP");
-        const bool fon = !(fe && fe[0] == '0');
-        std::vector<uint8_t> fskip((size_t)S.nsn, 0);
-        c->famt_grp.assign((size_t)S.nlev, csp_ctx::LfspGroups());
-        c->famt_any_groups = false;
-        for (int64_t l = 1; l < S.nlev && fon; ++l) {
-          const LevelClass& L = c->lvl[l];
-          if (!L.nS) continue;
-          const int nat = std::max(1, (L.famna + 15) / 16);
-          if (nat > 4 || !famt_grp_fits(nat, std::max(1, L.famcnn))) continue;
-          const int64_t b = S.levptr[l] + (L.nI - L.nS);
-          std::vector<int32_t> gptr(1, 0), glist;
-          std::vector<uint8_t> taken((size_t)L.nS, 0);
-          bool shared = false;
-          std::unordered_map<int64_t, std::vector<int64_t>> sibs;
-          for (int64_t q = 0; q < L.nS; ++q) sibs[S.snpar[lev2[b + q]]].push_back(q);
-          for (int64_t q = 0; q < L.nS; ++q) {
-            if (taken[(size_t)q]) continue;
-            const int32_t k = lev2[b + q];
-            taken[(size_t)q] = 1;
-            glist.push_back((int32_t)q);
-            int size = 1;
-            const int64_t par = S.snpar[k];
-            if (par >= 0 && is_large[(size_t)par]) {
-              const std::vector<int64_t>& sb = sibs[par];
-              for (auto it = std::upper_bound(sb.begin(), sb.end(), q); it != sb.end() && size < FAMT_GMAX; ++it) {
-                const int64_t q2 = *it;
-                const int32_t k2 = lev2[b + q2];
-                if (taken[(size_t)q2] || S.na(k2) != S.na(k)) continue;
-                if (!std::equal(S.relidx.begin() + S.sepptr[k], S.relidx.begin() + S.sepptr[k + 1], S.relidx.begin() + S.sepptr[k2])) continue;
-                taken[(size_t)q2] = 1;
-                glist.push_back((int32_t)q2);
-                fskip[(size_t)k2] = 1;
-                ++size;
-              }
-            }
-            gptr.push_back((int32_t)glist.size());
-            if (size > 1) shared = true;
-          }
-          if (!shared) {
-            for (int64_t q = 0; q < L.nS; ++q) fskip[(size_t)lev2[b + q]] = 0;
-            continue;
-          }
-          csp_ctx::LfspGroups& G = c->famt_grp[(size_t)l];
-          if ((rc = dev_upload(&G.ptr, gptr, D.bytes))) return rc;
-          if ((rc = dev_upload(&G.list, glist, D.bytes))) return rc;
-          G.ngroups = (int)gptr.size() - 1;
-          c->famt_any_groups = true;
-        }
-        if (c->famt_any_groups) {
-          if ((rc = dev_upload(&D.famt_skip, fskip, D.bytes))) return rc;
-          std::vector<uint8_t> both(fskip);
-          if (c->lfsp_any_groups) for (size_t i = 0; i < both.size(); ++i) both[i] |= skip[i];
-          if ((rc = dev_upload(&D.both_skip, both, D.bytes))) return rc;
-        }
-      }
-      lev3.insert(lev3.end(), large.begin(), large.end());
-      if ((rc = dev_upload(&D.lev3idx, lev3, D.bytes))) return rc;
-      D.lfd_len = (int64_t)(slot + 1) * 64 * 64;
-      if ((rc = dev_alloc(&D.lfd, (int64_t)(slot + 1) * 64 * 64, D.bytes))) return rc;
-      D.lfd_dense = D.lfd + (int64_t)slot * 64 * 64;
-    }
-    if ((rc = dev_upload(&D.cl, cl, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.rowidx, S.rowidx, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.relidx, S.relidx, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.chidx, ch, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.levidx, lev, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.lev2idx, lev2, D.bytes))) return rc;
-    clk.mark("descriptors + uploads");
-    // ---- gather plans for the extend-add
-    if (S.updplen() < (int64_t)1 << 31) {
-      std::vector<int64_t> tptr(S.nsn + 1, 0), cptr;
-      std::vector<int32_t> tgt, src;
-      const int64_t nsn1 = S.nsn / c->ntrial;       // a replicated pattern: plan of the first copy, shifted for the others
-      // (target code, src offset) pairs of every clique with children, sorted per clique: the cliques are independent,
-      // so host threads take them round-robin (5.5 M pairs on synth50k: 0.2 s of the set-up on one thread)
-      std::vector<int64_t> par;
-      for (int64_t k = 0; k < nsn1; ++k) if (S.chptr[k + 1] > S.chptr[k] || (cl[(size_t)k].pad >= 0 && S.na(k) > 0)) par.push_back(k);
-      std::vector<std::vector<std::pair<int32_t, int32_t>>> prs(par.size());
-      std::vector<int64_t> ntg(par.size(), 0);     // distinct targets per clique
-      // Large fronts list EVERY position of the lower triangle of their update block as a target, with or without
-      // contributions (marker pairs, dropped again when the sources are laid out): the plan kernels then assign the whole block
-      // and the clear pass before them (k_lf_clear_upd: a 5 us launch in every chain over the top fronts) is not needed
-      constexpr int32_t PLAN_MARK = INT32_MIN;
-      std::vector<int64_t> nmark(par.size(), 0);
-      {
-        const unsigned hw = std::thread::hardware_concurrency();
-        const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), (int64_t)16, (int64_t)par.size() / 64 + 1}));
-        auto work = [&](int tix) {
-          for (size_t x = (size_t)tix; x < par.size(); x += (size_t)nth) {
-            const int64_t k = par[x];
-            auto& pr = prs[x];
-            const int64_t nnp = S.nn(k);
-            size_t tot = 0;
-            for (int64_t q = S.chptr[k]; q < S.chptr[k + 1]; ++q) { const int64_t nac = S.na(S.chidx[q]); tot += (size_t)(nac * (nac + 1) / 2); }
-            pr.reserve(tot);
-            for (int64_t q = S.chptr[k]; q < S.chptr[k + 1]; ++q) {
-              const int64_t cc = S.chidx[q], nac = S.na(cc);
-              const int32_t* rel = &S.relidx[S.sepptr[cc]];
-              for (int64_t j = 0; j < nac; ++j)
-                for (int64_t i = j; i < nac; ++i) {
-                  int32_t ri = rel[i], rj = rel[j];
-                  int32_t code = rj < nnp ? (ri | (rj << 15)) : ((1 << 30) | (ri - (int32_t)nnp) | ((rj - (int32_t)nnp) << 15));
-                  pr.emplace_back(code, (int32_t)(S.updpptr[cc] + j * nac - j * (j - 1) / 2 + (i - j)));
-                }
-            }
-            if (cl[(size_t)k].pad >= 0) {
-              const int64_t nak = S.na(k);
-              for (int64_t j = 0; j < nak; ++j)
-                for (int64_t i = j; i < nak; ++i) pr.emplace_back((int32_t)((1 << 30) | (int32_t)i | ((int32_t)j << 15)), PLAN_MARK);
-              nmark[x] = nak * (nak + 1) / 2;
-            }
-            std::sort(pr.begin(), pr.end());
-            int64_t nd = 0;
-            for (size_t e = 0; e < pr.size(); ++e) if (e == 0 || pr[e].first != pr[e - 1].first) ++nd;
-            ntg[x] = nd;
-          }
-        };
-        run_threads(nth, work);
-      }
-      clk.mark("plan: sorted pairs");
-      // targets (distinct codes) per clique were counted by the workers: the serial part only lays the pieces out
-      std::vector<int64_t> tbase(par.size() + 1, 0), sbase(par.size() + 1, 0);
-      for (size_t x = 0; x < par.size(); ++x) { tbase[x + 1] = tbase[x] + ntg[x]; sbase[x + 1] = sbase[x] + (int64_t)prs[x].size() - nmark[x]; }
-      const int64_t nt1 = tbase[par.size()], ns1 = sbase[par.size()];
-      tgt.resize((size_t)nt1);
-      src.resize((size_t)ns1);
-      cptr.assign((size_t)nt1 + 1, 0);
-      {
-        const int nth2 = (int)std::max<int64_t>(1, std::min<int64_t>(16, (int64_t)par.size() / 64 + 1));
-        auto fill = [&](int tix) {
-          for (size_t x = (size_t)tix; x < par.size(); x += (size_t)nth2) {
-            const auto& pr = prs[x];
-            int64_t tq = tbase[x];
-            const int64_t s0 = sbase[x];
-            int64_t w = 0;
-            for (size_t e = 0; e < pr.size(); ++e) {
-              if (e == 0 || pr[e].first != pr[e - 1].first) { tgt[(size_t)tq] = pr[e].first; cptr[(size_t)tq] = s0 + w; ++tq; }
-              if (pr[e].second != PLAN_MARK) src[(size_t)(s0 + w++)] = pr[e].second;
-            }
-          }
-        };
-        run_threads(nth2, fill);
-      }
-      cptr[(size_t)nt1] = ns1;
-      {
-        size_t x = 0;
-        for (int64_t k = 0; k < nsn1; ++k) {
-          if (x < par.size() && par[x] == k) ++x;
-          tptr[k + 1] = tbase[x];
-        }
-      }
-      prs.clear();
-      clk.mark("plan: merge");
-      if (c->ntrial > 1) {
-        // a replicated pattern: the copies' plans are the first one shifted -- laid out on the device by one kernel
-        // (K = 8 on synth50k: 44 M indices; building them on the host and uploading 176 MB took 0.12 s)
-        const int64_t K = c->ntrial, up1 = S.updplen() / K;
-        for (int64_t t = 1; t < K; ++t)
-          for (int64_t k = 0; k < nsn1; ++k) tptr[t * nsn1 + k + 1] = tptr[k + 1] + t * nt1;
-        if ((rc = dev_upload(&D.gp_tptr, tptr, D.bytes))) return rc;
-        if ((rc = dev_alloc(&D.gp_tgt, nt1 * K, D.bytes))) return rc;
-        if ((rc = dev_alloc(&D.gp_cptr, nt1 * K + 1, D.bytes))) return rc;
-        if ((rc = dev_alloc(&D.gp_src, ns1 * K, D.bytes))) return rc;
-        if (nt1) HIPCHK(hipMemcpy(D.gp_tgt, tgt.data(), sizeof(int32_t) * nt1, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(D.gp_cptr, cptr.data(), sizeof(int64_t) * (nt1 + 1), hipMemcpyHostToDevice));
-        if (ns1) HIPCHK(hipMemcpy(D.gp_src, src.data(), sizeof(int32_t) * ns1, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_replicate_plan, dim3(2048), dim3(256), 0, 0, D.gp_tgt, D.gp_cptr, D.gp_src, nt1, ns1, up1, K);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        clk.mark("plan: replicate (device)");
-      } else {
-        if ((rc = dev_upload(&D.gp_tptr, tptr, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.gp_tgt, tgt, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.gp_cptr, cptr, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.gp_src, src, D.bytes))) return rc;
-      }
-    }
-    c->plan_full_upd = true;
-    clk.mark("plan: upload");
-    if ((rc = dev_alloc(&D.lk, S.blklen(), D.bytes))) return rc;
-    HIPCHK(hipMemset(D.lk, 0, sizeof(double) * std::max<int64_t>(S.blklen(), 1)));
-    static bool attrs_done = false;     // function attributes are per process (one device per process): set them once
-    if (!attrs_done) {
-      attrs_done = true;
-      const int mx = 160 * 1024 - 1024;
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_pad, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<3, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_n16<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_partial<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_partial<false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<1, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<2, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<3, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<3, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<5, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<5, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<6, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<7, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_gram_diag128<9, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_lf_diag, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_factor_yaa_lds, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_down_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_down_mfma<true, WK_DOWN0>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_chol_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_chol_mfma<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_pinv_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_down_inv_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_hess_up_inv_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_llt_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-      HIPCHK(hipFuncSetAttribute((const void*)k_completion_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx));
-    }
-    if ((rc = dev_upload(&D.tmpptr, c->h_tmpptr, D.bytes))) return rc;
-    if ((rc = dev_alloc(&D.yaa, S.updlen(), D.bytes))) return rc;
-    if ((rc = dev_alloc(&D.fac, S.updlen(), D.bytes))) return rc;
-    HIPCHK(hipMemset(D.fac, 0, sizeof(double) * std::max<int64_t>(S.updlen(), 1)));     // strict upper triangles stay zero (prepare_yaa)
-    if (!D.sw) {
-      if ((rc = dev_alloc(&D.sw, S.blklen(), D.bytes))) return rc;
-      hipLaunchKernelGGL(k_fill_sqrt_weights, dim3((unsigned)std::min<int64_t>(S.nsn, 4096)), dim3(256), 0, 0, D.cl, (int)S.nsn, D.sw);
-    }
-    if ((rc = dev_alloc(&D.faci, S.updlen(), D.bytes))) return rc;
-    if ((rc = dev_alloc(&D.red, 4096, D.bytes))) return rc;      // [0, 1024): reduction scratch, [1024, 4096): shares of a split Amap (kkt_solve)
-    if ((rc = dev_alloc(&D.info, 32, D.bytes))) return rc;      // [0, 16): failure flags of the copies; [16]: status latch
-    HIPCHK(hipMemset(D.info, 0, sizeof(int) * 32));
-    // pinned mirror: ints [0, 16) the trial flags (csp_trial_flags), [16] the status latch (csp_status), bytes [96, 104) the
-    // scalar of the reductions (csp_dot / csp_logdiagsum): separate slots, so that no call overwrites another's result
-    HIPCHK(hipHostMalloc((void**)&D.info_host, 128));
-    clk.mark("attributes + buffers");
-    { hipDeviceProp_t p; D.ncu = (hipGetDeviceProperties(&p, device) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
-    D.device = device;
-  } else {
-    if (D.upd) { hipFree(D.upd); D.bytes -= D.max_rhs * S.updlen() * 8; D.upd = nullptr; }
-    if (D.updp) { hipFree(D.updp); D.bytes -= D.max_rhs * D.updp_stride * 8; D.updp = nullptr; }
-    if (D.tmp) { hipFree(D.tmp); D.bytes -= D.max_rhs * D.tmplen * 8; D.tmp = nullptr; }
-  }
-  int rc = 0;
-  if ((rc = dev_alloc(&D.upd, max_rhs * S.updlen(), D.bytes))) return rc;
-  { const char* e = sw_str("SMCP_UPDP_PAD"); D.updp_stride = S.updplen() + (e ? std::max(0, atoi(e)) : 0); }
-  if ((rc = dev_alloc(&D.updp, max_rhs * D.updp_stride, D.bytes))) return rc;
-  if ((rc = dev_alloc(&D.tmp, max_rhs * D.tmplen, D.bytes))) return rc;
-  D.max_rhs = max_rhs;
-  clk.mark("per-rhs workspaces");
-  return 0;
-}
+#include "setup.hip"
 
-int64_t csp_device_bytes(const csp_ctx* c) { return c ? c->D.bytes : 0; }
+extern "C" {
+
+int64_t csp_device_bytes(const csp_ctx* c) { return c ? c->D.mem.total : 0; }
 
 static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set, bool li_last = false);
 int csp_cholesky(csp_ctx* c, double* x, void* stream) { return cholesky_impl(c, x, stream, 0); }
@@ -3163,7 +2556,7 @@ int trsm_impl(csp_ctx* c, const double* L, const double* Y, double* B, int64_t n
     // clique's triangle by substitution in one workgroup per sixteen columns -- 0.48 ms per level on config 4
     if (int rc = prep_lk_cached(c, L, Y, st)) return rc;
     DeviceCtx& D = c->D;
-    if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, ldb * nrhs, D.bytes, st)) return rc;
+    if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, ldb * nrhs, D.mem, st)) return rc;
     MfmaArgs a0 = mfma_args(c, nullptr, 0, (int)nrhs);
     const unsigned ct = (unsigned)tiles64((int)nrhs);
     auto level = [&](int64_t l) {
@@ -3286,9 +2679,9 @@ static int tune_placement(csp_ctx* c, int tries) {
   if (par.size() < 64) return 0;               // no family sweep worth tuning for
   D.qr_valid = false;                          // the probe overwrites panels of the stack (Q of kkt_qr lives there)
   D.lg_nochild = false;
-  int32_t* dpar = nullptr;
-  int64_t junk = 0;
-  if (int rc = dev_upload(&dpar, par, junk)) return rc;
+  int32_t* dpar = nullptr;      // (a temporary of this function, not the context's: allocated and freed directly)
+  if (hipMalloc((void**)&dpar, par.size() * sizeof(int32_t)) != hipSuccess) return SMCP_ENOMEM;
+  if (hipMemcpy(dpar, par.data(), par.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(dpar); return SMCP_EHIP; }
   HIPCHK(hipDeviceSynchronize());
   hipEvent_t e0, e1;
   HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
@@ -3308,7 +2701,7 @@ static int tune_placement(csp_ctx* c, int tries) {
   float best = 0.f;
   int rc = probe(best);
   const float first = best;
-  std::vector<void*> rejected;                 // kept until the end: a freed buffer would be handed out again at once
+  std::vector<double*> rejected;               // kept until the end: a freed buffer would be handed out again at once
   // The probe stores into BOTH buffers -- the packed updates and the panels of the swept stack -- and either can lie badly
   // (probe levels seen: 0.38 both well placed, 0.42-0.44 one of them, 0.50 neither): the tries alternate between them, the
   // stack only while the buffers set aside stay under 16 GB.  The CONTENTS of both buffers are NOT preserved: the probe
@@ -3324,9 +2717,9 @@ static int tune_placement(csp_ctx* c, int tries) {
     const size_t bytes = stack ? sbytes : ubytes;
     double* old = slot;
     double* nu = nullptr;
-    if (hipMalloc((void**)&nu, bytes) != hipSuccess) { (void)hipGetLastError(); break; }   // out of memory: keep what we have (and leave no sticky error behind)
+    if (dev_malloc(D.mem, (void**)&nu, bytes) != hipSuccess) { (void)hipGetLastError(); break; }   // out of memory: keep what we have (and leave no sticky error behind)
     // (the copy keeps the never-written entries of the stack finite, which is all the sweeps ask of it)
-    if (stack && hipMemcpy(nu, old, bytes, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(nu); rc = SMCP_EHIP; break; }
+    if (stack && hipMemcpy(nu, old, bytes, hipMemcpyDeviceToDevice) != hipSuccess) { (void)dev_free(D.mem, nu); rc = SMCP_EHIP; break; }
     slot = nu;
     float ms = 0.f;
     rc = probe(ms);
@@ -3335,7 +2728,7 @@ static int tune_placement(csp_ctx* c, int tries) {
     held += bytes;
     if (best <= 0.80f * first) break;          // from the slow end of the spread to the fast one: good enough
   }
-  for (void* p : rejected) (void)hipFree(p);
+  for (double*& p : rejected) (void)dev_free(D.mem, p);      // (the kept buffers stay recorded)
   (void)hipFree(dpar);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   static int verbose = -1;
@@ -3365,8 +2758,8 @@ int csp_tune(csp_ctx* c, int what, int64_t value) {
     case CSP_TUNE_VERIFY_CACHE:
       if (c->D.device < 0) return SMCP_ENODEV;
       if (value && !c->D.fp) {
-        if (hipMalloc((void**)&c->D.fp, 8 * sizeof(unsigned long long)) != hipSuccess) return SMCP_ENOMEM;
-        if (hipMalloc((void**)&c->D.fp_bad, sizeof(int)) != hipSuccess) return SMCP_ENOMEM;
+        if (int rc = dev_alloc(&c->D.fp, 8, c->D.mem)) return rc;
+        if (int rc = dev_alloc(&c->D.fp_bad, 1, c->D.mem)) return rc;
         if (hipMemset(c->D.fp, 0, 8 * sizeof(unsigned long long)) != hipSuccess || hipMemset(c->D.fp_bad, 0, sizeof(int)) != hipSuccess) return SMCP_EHIP;
       }
       c->verify_cache = value != 0;
@@ -3420,79 +2813,6 @@ int64_t csp_profile_read(csp_ctx* c, double* ms, int64_t* count) {
   return KID_COUNT;
 }
 
-// placement studies (scratch/famt_realloc2.py): move one of the big work buffers to a fresh allocation -- 0 the packed
-// exchange buffer (updp), 1 the constraint stack (ustack); `shift` bytes are allocated first and freed afterwards so that
-// the new buffer lands elsewhere.  Not part of the documented boundary.
-// store pattern of the family sweep without its arithmetic: one wave per (slot, right-hand side), eight right-hand sides in
-// flight per workgroup, a 9.5 KB run into the stack and a 16.6 KB run into the exchange buffer per pair
-__global__ void __launch_bounds__(512) k_probe_streams(double* ustack, int64_t bl, double* updp, int64_t ustride, int nslots, int nrhs,
-                                                        int64_t blk0, int64_t upd0) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int p = blockIdx.x;
-  for (int r = blockIdx.y + gridDim.y * wave; r < nrhs; r += gridDim.y * 8) {
-    double* P = ustack + (int64_t)r * bl + blk0 + (int64_t)p * 1185;
-    double* U = updp + (int64_t)r * ustride + upd0 + (int64_t)p * 2080;
-    for (int e = lane; e < 1185; e += 64) P[e] = 1.0;
-    for (int e = lane; e < 2080; e += 64) U[e] = 1.0;
-  }
-}
-int csp_debug_realloc(csp_ctx* c, int which, int64_t shift) {
-  if (int rc = ready(c)) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  DeviceCtx& D = c->D;
-  if (which == 20) {      // probe: the store pattern of the family sweep on the buffers as they lie (synth50k geometry)
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    const int nrhs = (int)std::min<int64_t>(D.max_rhs, D.ustack_cols);
-    const int64_t blk0 = 7168 * 180, upd0 = (int64_t)7168 * 496;
-    if ((int64_t)896 * 1185 + blk0 > c->S.blklen() || (int64_t)896 * 2080 + upd0 > c->S.updplen()) return SMCP_EINVAL;
-    hipLaunchKernelGGL(k_probe_streams, dim3(896, 2), dim3(512), 0, 0, D.ustack, c->S.blklen(), D.updp, D.updp_stride, 896, nrhs, blk0, upd0);
-    HIPCHK(hipEventRecord(e0, 0));
-    for (int r = 0; r < 3; ++r)
-      hipLaunchKernelGGL(k_probe_streams, dim3(896, 2), dim3(512), 0, 0, D.ustack, c->S.blklen(), D.updp, D.updp_stride, 896, nrhs, blk0, upd0);
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    fprintf(stderr, "smcp_amd: store-pattern probe: %.3f ms per pass  ustack %p updp %p\n", ms / 3, (void*)D.ustack, (void*)D.updp);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 0;
-  }
-  if (which >= 10) {      // probe: milliseconds of a linear fill of the buffer (which - 10), printed
-    double* p = which == 10 ? D.updp : D.ustack;
-    const size_t bytes = sizeof(double) * (size_t)(which == 10 ? D.max_rhs * D.updp_stride : D.ustack_cols * c->S.blklen());
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipMemsetAsync(p, 0, bytes, 0));
-    HIPCHK(hipEventRecord(e0, 0));
-    for (int r = 0; r < 3; ++r) HIPCHK(hipMemsetAsync(p, 0, bytes, 0));
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    fprintf(stderr, "smcp_amd: fill of %s: %.3f ms per pass, %.2f TB/s\n", which == 10 ? "updp" : "ustack", ms / 3, bytes / (ms / 3 * 1e-3) / 1e12);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 0;
-  }
-  void* dummy = nullptr;
-  if (shift > 0 && hipMalloc(&dummy, (size_t)shift) != hipSuccess) return SMCP_ENOMEM;
-  int64_t junk = 0;
-  if (which == 0) {
-    double* nu = nullptr;
-    if (dev_alloc(&nu, D.max_rhs * D.updp_stride, junk)) return SMCP_ENOMEM;
-    HIPCHK(hipFree(D.updp));
-    D.updp = nu;
-  } else {
-    double* nu = nullptr;
-    const int64_t len = D.ustack_cols * c->S.blklen();
-    if (dev_alloc(&nu, len, junk)) return SMCP_ENOMEM;
-    HIPCHK(hipMemset(nu, 0, sizeof(double) * len));
-    HIPCHK(hipFree(D.ustack));
-    D.ustack = nu;
-  }
-  if (dummy) HIPCHK(hipFree(dummy));
-  return 0;
-}
 int csp_debug_stamps(csp_ctx* c, unsigned long long* out, int reset) {
   if (int rc = ready(c)) return rc;
   HIPCHK(hipDeviceSynchronize());

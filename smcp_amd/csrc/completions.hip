@@ -13,9 +13,9 @@ constexpr int64_t MRC_HBM_DOUBLES = (int64_t)1 << 25;  // HBM slots of one launc
 int mrc_setup(csp_ctx* c) {
   DeviceCtx& D = c->D;
   if (D.mrc.ints) return 0;
-  if (int rc = dev_alloc(&D.mrc.ints, 2 * c->S.nsn + 4, D.bytes)) return rc;
-  if (int rc = dev_alloc(&D.mrc.xdiag, c->S.n, D.bytes)) return rc;
-  return dev_alloc(&D.mrc.list, c->S.nsn, D.bytes);
+  if (int rc = dev_alloc(&D.mrc.ints, 2 * c->S.nsn + 4, D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.xdiag, c->S.n, D.mem)) return rc;
+  return dev_alloc(&D.mrc.list, c->S.nsn, D.mem);
 }
 
 // bytes of dynamic LDS a launch of Kern may ask for: MRC_LDS once the device has granted it to this kernel (asked on
@@ -47,7 +47,7 @@ int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need,
   if (q < e) {
     const int64_t slot = (need[e - 1] + 31) / 32 * 32;
     const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
-    if (int rc = dev_grow(&D.mrc.ws, &D.mrc.cap, G * slot, D.bytes, st)) return rc;
+    if (int rc = dev_grow(&D.mrc.ws, &D.mrc.cap, G * slot, D.mem, st)) return rc;
     a.lev = D.mrc.list + q;
     a.cnt = (int)(e - q);
     a.ws = D.mrc.ws;
@@ -203,11 +203,11 @@ int psd_setup(csp_ctx* c) {
     if (L.e2 > max_tasks) return SMCP_ENOMEM;
     if (L.e2 > L.b1) c->psd_lev.push_back(L);
   }
-  if (int rc = dev_upload(&P.tasks, tasks, D.bytes)) return rc;
-  if (int rc = dev_alloc(&P.w, S.blklen(), D.bytes)) return rc;
-  if (int rc = dev_alloc(&P.idx, S.sepptr[S.nsn], D.bytes)) return rc;
-  if (int rc = dev_alloc(&P.ra, S.nsn, D.bytes)) return rc;
-  return dev_upload(&P.ulist, ulist, D.bytes);      // last: ulist marks the plan as built
+  if (int rc = dev_upload(&P.tasks, tasks, D.mem)) return rc;
+  if (int rc = dev_alloc(&P.w, S.blklen(), D.mem)) return rc;
+  if (int rc = dev_alloc(&P.idx, S.sepptr[S.nsn], D.mem)) return rc;
+  if (int rc = dev_alloc(&P.ra, S.nsn, D.mem)) return rc;
+  return dev_upload(&P.ulist, ulist, D.mem);      // last: ulist marks the plan as built
 }
 
 }  // namespace

@@ -7,6 +7,7 @@
 #include <map>
 #include <vector>
 
+#include "devmem.hpp"
 #include "symbolic.hpp"
 
 namespace smcp {
@@ -27,20 +28,13 @@ struct CliqueDesc {
 
 struct PsdTask;
 
-// frees the device buffers named and clears the pointers
-template <class... T>
-inline void dev_release(T*&... p) {
-  ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
-}
-
-// Plans of the operations of csrc/products.hip and csrc/completions.hip: built on the first call of each, released once by
-// csp_symbolic_destroy.
+// Plans of the operations of csrc/products.hip and csrc/completions.hip: built on the first call of each; their buffers
+// live as long as the context (its ledger frees them).
 // A transposed row index (null until built): row i of the result owns the positions [tptr[i], tptr[i + 1]) of a list of all
 // contributions, in the order of its sum; pos: producer's slot -> position; heavy: the rows with long sums
 struct RowIndex {
   int64_t* tptr = nullptr; int32_t* pos = nullptr;
   int32_t* heavy = nullptr; int64_t nheavy = 0;
-  void release() { dev_release(tptr, pos, heavy); }
 };
 
 // products with the factor (front_trmm.hip): the transposed separator index (the contributions are all separator entries, a
@@ -52,7 +46,6 @@ struct TrmmPlan {
   RowIndex idx;
   int32_t* items[2] = {nullptr, nullptr}; int64_t nitems[2][2] = {{0, 0}, {0, 0}};
   int32_t* tiles[2] = {nullptr, nullptr}; int64_t ntiles[2][2] = {{0, 0}, {0, 0}};
-  void release() { idx.release(); dev_release(items[0], items[1], tiles[0], tiles[1]); }
 };
 
 // rank-k updates on the pattern (front_syr2k.hip): (clique, row chunk, column chunk, zero) items of the FMA kernel, those of
@@ -62,7 +55,6 @@ struct Syr2kPlan {
   bool ready = false;
   int32_t* items = nullptr; int64_t nitems[2] = {0, 0};
   int32_t* tiles = nullptr; int64_t ntiles[2] = {0, 0};
-  void release() { dev_release(items, tiles); }
 };
 
 // products of the matrix itself (front_symm.hip): the contribution index (the contributions are all ntot partials; pos: per
@@ -73,7 +65,6 @@ struct SymmPlan {
   RowIndex idx;
   int32_t* items = nullptr; int64_t nitems[2] = {0, 0};
   int64_t ntot = -1;
-  void release() { idx.release(); dev_release(items); }
 };
 
 // minimum-rank, distance-matrix and dense PSD completion (front_mrc.hip, front_edm.hip, front_psd.hip): per-workgroup HBM
@@ -82,7 +73,6 @@ struct SymmPlan {
 struct CompletionWs {
   double* ws = nullptr; int64_t cap = 0;
   int32_t* ints = nullptr; double* xdiag = nullptr; int32_t* list = nullptr;
-  void release() { dev_release(ws, ints, xdiag, list); cap = 0; }
 };
 
 // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
@@ -90,56 +80,13 @@ struct CompletionWs {
 struct PsdPlan {
   PsdTask* tasks = nullptr; int32_t* ulist = nullptr;
   double* w = nullptr; int32_t* idx = nullptr; int32_t* ra = nullptr;
-  void release() { dev_release(tasks, ulist, w, idx, ra); }
 };
 
-struct DeviceCtx {
-  int device = -1;
-  int ncu = 256;           // compute units of the device (csp_device_init): launch heuristics
-  int64_t max_rhs = 0;
-  // index arrays
-  CliqueDesc* cl = nullptr;
-  int32_t* rowidx = nullptr;
-  int32_t* relidx = nullptr;
-  int32_t* chidx = nullptr;
-  int32_t* levidx = nullptr;  // cliques sorted by level
-  int32_t* lev2idx = nullptr; // per level: LDS-class cliques first, then HBM-class
-  // extend-add gather plans (deterministic, atomic-free): per clique with children, the list of
-  // front positions that receive contributions and, per position, the update-workspace offsets
-  // of the children's entries that map onto it
-  int64_t* gp_tptr = nullptr;  // nsn+1 : first target of clique k
-  int32_t* gp_tgt = nullptr;   // target code: bit 30 = update-matrix block, i | j << 15
-  int64_t* gp_cptr = nullptr;  // ntargets+1 : first contribution of target t
-  int32_t* gp_src = nullptr;   // offset of the contributing entry in the (per right-hand side) update workspace
-  // validity tags of the cached inverse-form factor / Y_AA blocks: the buffers they were derived
-  // from.  Every in-place factor operation on a buffer clears the tags that mention it.
-  const void* lk_tag_L = nullptr;   // LK was prepared from the factor stored at this address ...
-  const void* lk_tag_Y = nullptr;   // ... or from the factor whose projected inverse now lives here
-  const void* yaa_tag = nullptr;    // yaa holds the separator blocks of the matrix at this address
-  const void* fac_tag = nullptr;    // fac = chol(yaa) of the matrix at this address
-  bool fac_partial = false;         // ... except for the family children (childless small cliques whose Gram block comes from
-                                    // k_leaf_pairs: nothing reads their factors on that route); complete_fac fills them in
-  const void* faci_tag = nullptr;   // faci = fac^-1 of the matrix at this address
-  double* lfd = nullptr;      // 64 x 64 doubles per large front: inverse of the current diagonal block
-  int32_t* lev3idx = nullptr; // all LDS-class cliques (any level), then all large fronts: lists for clique-local kernels
-  int64_t nI_total = 0, nII_total = 0;
-  int nnmaxII_all = 0, namaxII_all = 0;   // maxima over the large fronts
-  double* lfd_dense = nullptr;            // the 64 x 64 slot used by the dense (Schur complement) Cholesky
-  double* lk = nullptr;       // inverse-form factor [L_NN^-1; L_AN L_NN^-1] of the most recent prep
-  // workspaces
-  double* upd = nullptr;   // max_rhs * updlen : update matrices
-  double* updp = nullptr;  // max_rhs * updplen : packed lower triangles handed from children to parents (fast up-sweeps, cholesky)
-  double* yaa = nullptr;   // updlen : Y[A_k,A_k] cache (Hessian)
-  double* fac = nullptr;   // updlen : chol(Y_AA) cache
-  double* faci = nullptr;  // updlen : inverse of fac (lower; positions above the diagonal are scratch)
-  double* tmp = nullptr;   // max_rhs * tmplen : per-clique scratch (tmpptr)
-  int64_t* tmpptr = nullptr;
-  int64_t tmplen = 0;
-  double* red = nullptr;   // reduction scratch
-  int* info = nullptr;     // device failure flag
-  unsigned long long* fp = nullptr; int* fp_bad = nullptr;   // cache verification: latched fingerprints [0..3], scratch [4..7], mismatch flag
-  int* info_host = nullptr;  // pinned host mirror
-  // constraints
+// ---- buffers whose lifetime is shorter than the context's: each group is replaced as a whole; release() frees its buffers
+// through the ledger and resets the group to its defaults
+// What kkt_set_constraints builds, with the counts and flags that describe it.  (Statistics of the entry tables that
+// survive a re-set -- kc_maxlist, fam_maxterms, kc_sorted, lg_rec ... -- stay in DeviceCtx.)
+struct ConstraintBufs {
   int64_t m = 0, cnnz = 0;
   int64_t* cptr = nullptr;   // CSC by constraint (m+1)
   int64_t* cidx = nullptr;   // blkval positions
@@ -171,21 +118,14 @@ struct DeviceCtx {
   // k_famt_prep), static term lists per (family, constraint); fz_ok: every family parent hangs under a front the LDS extend-add takes
   int32_t* fz_no = nullptr; int32_t* fz_slot = nullptr; int32_t* fz_ptr = nullptr; int32_t* fz_pk = nullptr; double* fz_s = nullptr;
   int64_t fz_nfam = 0; bool fz_ok = false;
-  double* famc = nullptr;    // children's constants of the family parents of one sweep call, in LDS layout (k_fam2_prep)
-  int64_t famc_len = 0;
-  int64_t kc_maxlist = 0;    // longest entry list of a (clique, constraint) pair among possible family members
-  int64_t fam_maxterms = 0;  // most entries of a (family, constraint) pair: the parent's own + its children's
-  double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
   double* vbuf = nullptr;    // n x vcols : S^-1[:, K_s] of the chunk in flight
-  double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
   int64_t vcols = 0;
   double* hd = nullptr;      // md x md Gram block of the dense constraints (when ns > 0)
-  // blocked dense Cholesky of the Schur complement: inverses of its 64 x 64 diagonal blocks (for the blocked potrs)
-  double* hinv = nullptr;    // nblocks * 4096 + 2 n doubles (the tail holds the two work vectors of the solve)
-  int64_t hinv_cap = 0, hinv_n = 0;
-  const void* hinv_tag = nullptr;   // the factor these inverses belong to
-  double* h_pending = nullptr; int64_t h_pending_n = 0, h_pending_ld = 0; hipStream_t h_pending_stream = nullptr;   // a Schur complement left unfactored by kkt_schur_factor (deferred status)
-  double* sw = nullptr;      // blklen : sqrt of the inner-product weights (Gram path)
+  int32_t* lg_eptr = nullptr; int32_t* lg_epk = nullptr; double* lg_ew = nullptr; int32_t* lg_remap = nullptr;   // static entry lists per family child
+  double* lg_tab = nullptr;  // per-step tables (Psi, Omega) of the family children, lg_rec doubles per child
+  int64_t lg_children = 0;   // family children (0: no closed-form Gram blocks)
+  bool lg_nochild = false;   // the last Schur sweep left the family children's panels out of the stack: their Gram block comes from k_leaf_gram
+  // scratch and tables of the Gram accumulation, sized by m and by the route the constraint set takes (grown by dev_grow)
   double* gpart = nullptr;   // partial Gram tiles
   int64_t gpart_len = 0;
   // Gram accumulation over slices of the stack (k_gram_diag128) and closed-form blocks of the family children
@@ -193,20 +133,90 @@ struct DeviceCtx {
   int64_t* gsl_start = nullptr; int32_t* gsl_len = nullptr; int64_t gsl_cap = 0; int gsl_n = 0;
   int gsl_spw = 0, gsl_early = 0;    // table built early rows first: slices per chunk and chunks of the early part (0: plain table)
   int32_t* lg_list = nullptr; int32_t* lg_slot = nullptr; int64_t lg_cap = 0; int lg_cnt = 0;     // family children inside the ranges, their index among all of them
-  int32_t* lg_eptr = nullptr; int32_t* lg_epk = nullptr; double* lg_ew = nullptr; int32_t* lg_remap = nullptr;   // static entry lists per family child
-  double* lg_tab = nullptr; int lg_rec = 0;                           // per-step tables (Psi, Omega), lg_rec doubles per child
-  int lg_nf = 0, lg_nn = 0, lg_na = 0;                                // sizing over that list
-  int64_t lg_children = 0, lg_maxent = 0, lg_pairs = 0, lg_rows = 0;  // over all family children (kkt_set_constraints)
-  const double* part_Y = nullptr;   // the Y of the last kkt_prepare_part (sharded step): valid while part_valid
-  int64_t updp_stride = 0;          // doubles between the packed exchange buffers of consecutive right-hand sides (>= updplen)
   int32_t* scm_owner = nullptr;     // per constraint: the part that computes its SCMcolumn2 columns (kkt_schur_gram_part), -1 = swept
-  bool kc_sorted = false;    // every per-(clique, constraint) entry list ascends in panel position (columns are contiguous runs)
-  bool lg_request = false;   // the running Schur sweep may leave the panels of the family children out
-  bool lg_nochild = false;   // ... and did: the stack lacks them, their Gram block comes from k_leaf_gram
   // kkt_qr (csrc/kkt_qr.hip): m x m work matrices, the inverse of the triangular factor, G(bx) and reduction scratch;
   // the orthonormal factor Q itself overwrites ustack
   double* qr_ws = nullptr;
   int64_t qr_len = 0;
+  bool qr_valid = false;       // ustack holds Q and qr_ws the factor for the matrices (qr_L, qr_Y)
+  void release(DevLedger& mem) {
+    dev_free(mem, cptr, cidx, cval, cwval, rpos, rptr, rcon, rval, ustack, a_r, a_c, s_rloc, s_cloc, dlist, slist, kidx);
+    dev_free(mem, kc_ptr, kc_off, kc_val, kc_ij, fz_no, fz_slot, fz_ptr, fz_pk, fz_s, vbuf, hd);
+    dev_free(mem, lg_eptr, lg_epk, lg_ew, lg_remap, lg_tab, scm_owner, qr_ws, gpart, gsl_start, gsl_len, lg_list, lg_slot);
+    *this = ConstraintBufs();
+  }
+};
+// Workspaces sized by max_rhs: replaced when csp_device_init is asked for more right-hand sides
+struct RhsWorkspaces {
+  int64_t max_rhs = 0;
+  double* upd = nullptr;   // max_rhs * updlen : update matrices
+  double* updp = nullptr;  // max_rhs * updplen : packed lower triangles handed from children to parents (fast up-sweeps, cholesky)
+  double* tmp = nullptr;   // max_rhs * tmplen : per-clique scratch (tmpptr)
+  void release(DevLedger& mem) { dev_free(mem, upd, updp, tmp); *this = RhsWorkspaces(); }
+};
+
+struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
+  DevLedger mem;           // every device buffer this context holds (devmem.hpp)
+  int device = -1;
+  int ncu = 256;           // compute units of the device (csp_device_init): launch heuristics
+  // index arrays
+  CliqueDesc* cl = nullptr;
+  int32_t* rowidx = nullptr;
+  int32_t* relidx = nullptr;
+  int32_t* chidx = nullptr;
+  int32_t* levidx = nullptr;  // cliques sorted by level
+  int32_t* lev2idx = nullptr; // per level: LDS-class cliques first, then HBM-class
+  // extend-add gather plans (deterministic, atomic-free): per clique with children, the list of
+  // front positions that receive contributions and, per position, the update-workspace offsets
+  // of the children's entries that map onto it
+  int64_t* gp_tptr = nullptr;  // nsn+1 : first target of clique k
+  int32_t* gp_tgt = nullptr;   // target code: bit 30 = update-matrix block, i | j << 15
+  int64_t* gp_cptr = nullptr;  // ntargets+1 : first contribution of target t
+  int32_t* gp_src = nullptr;   // offset of the contributing entry in the (per right-hand side) update workspace
+  // validity tags of the cached inverse-form factor / Y_AA blocks: the buffers they were derived
+  // from.  Every in-place factor operation on a buffer clears the tags that mention it.
+  const void* lk_tag_L = nullptr;   // LK was prepared from the factor stored at this address ...
+  const void* lk_tag_Y = nullptr;   // ... or from the factor whose projected inverse now lives here
+  const void* yaa_tag = nullptr;    // yaa holds the separator blocks of the matrix at this address
+  const void* fac_tag = nullptr;    // fac = chol(yaa) of the matrix at this address
+  bool fac_partial = false;         // ... except for the family children (childless small cliques whose Gram block comes from
+                                    // k_leaf_pairs: nothing reads their factors on that route); complete_fac fills them in
+  const void* faci_tag = nullptr;   // faci = fac^-1 of the matrix at this address
+  double* lfd = nullptr;      // 64 x 64 doubles per large front: inverse of the current diagonal block
+  int32_t* lev3idx = nullptr; // all LDS-class cliques (any level), then all large fronts: lists for clique-local kernels
+  int64_t nI_total = 0, nII_total = 0;
+  int nnmaxII_all = 0, namaxII_all = 0;   // maxima over the large fronts
+  double* lfd_dense = nullptr;            // the 64 x 64 slot used by the dense (Schur complement) Cholesky
+  double* lk = nullptr;       // inverse-form factor [L_NN^-1; L_AN L_NN^-1] of the most recent prep
+  // workspaces
+  double* yaa = nullptr;   // updlen : Y[A_k,A_k] cache (Hessian)
+  double* fac = nullptr;   // updlen : chol(Y_AA) cache
+  double* faci = nullptr;  // updlen : inverse of fac (lower; positions above the diagonal are scratch)
+  int64_t* tmpptr = nullptr;
+  int64_t tmplen = 0;
+  double* red = nullptr;   // reduction scratch
+  int* info = nullptr;     // device failure flag
+  unsigned long long* fp = nullptr; int* fp_bad = nullptr;   // cache verification: latched fingerprints [0..3], scratch [4..7], mismatch flag
+  int* info_host = nullptr;  // pinned host mirror
+  double* famc = nullptr;    // children's constants of the family parents of one sweep call, in LDS layout (k_fam2_prep)
+  int64_t famc_len = 0;
+  int64_t kc_maxlist = 0;    // longest entry list of a (clique, constraint) pair among possible family members
+  int64_t fam_maxterms = 0;  // most entries of a (family, constraint) pair: the parent's own + its children's
+  double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
+  double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
+  // blocked dense Cholesky of the Schur complement: inverses of its 64 x 64 diagonal blocks (for the blocked potrs)
+  double* hinv = nullptr;    // nblocks * 4096 + 2 n doubles (the tail holds the two work vectors of the solve)
+  int64_t hinv_cap = 0, hinv_n = 0;
+  const void* hinv_tag = nullptr;   // the factor these inverses belong to
+  double* h_pending = nullptr; int64_t h_pending_n = 0, h_pending_ld = 0; hipStream_t h_pending_stream = nullptr;   // a Schur complement left unfactored by kkt_schur_factor (deferred status)
+  double* sw = nullptr;      // blklen : sqrt of the inner-product weights (Gram path)
+  int lg_rec = 0;                                                     // doubles per child of the per-step tables (lg_tab)
+  int lg_nf = 0, lg_nn = 0, lg_na = 0;                                // sizing over that list
+  int64_t lg_maxent = 0, lg_pairs = 0, lg_rows = 0;                   // over all family children (kkt_set_constraints)
+  const double* part_Y = nullptr;   // the Y of the last kkt_prepare_part (sharded step): valid while part_valid
+  int64_t updp_stride = 0;          // doubles between the packed exchange buffers of consecutive right-hand sides (>= updplen)
+  bool kc_sorted = false;    // every per-(clique, constraint) entry list ascends in panel position (columns are contiguous runs)
+  bool lg_request = false;   // the running Schur sweep may leave the panels of the family children out (lg_nochild: and did)
   // sparse-input sweep of childless large fronts (front_lfsp.hip): R^T and R^T K of the current factors, the longest
   // entry list of such a front, and the generations of fac / lk they were formed from
   double* sp_rt = nullptr; double* sp_mk = nullptr;
@@ -220,7 +230,6 @@ struct DeviceCtx {
   int64_t kc_maxlist_large = 0;
   int64_t fac_gen = 0, lk_gen = 0, sp_fac_gen = -1, sp_lk_gen = -1;
   bool part_valid = false;     // lk / yaa / fac hold the sharded factor prepared by kkt_prepare_part (sets 2 then 1)
-  bool qr_valid = false;       // ustack holds Q and qr_ws the factor for the matrices (qr_L, qr_Y)
   const void* qr_L = nullptr; const void* qr_Y = nullptr;
   int64_t lfd_len = 0;         // doubles of lfd (large-front slots + the dense slot)
   CompletionWs mrc;
@@ -228,7 +237,6 @@ struct DeviceCtx {
   TrmmPlan trmm;
   Syr2kPlan syr2k;
   SymmPlan symm;
-  int64_t bytes = 0;
 };
 
 }  // namespace smcp
@@ -281,9 +289,23 @@ struct LevelSet {
 };
 }  // namespace smcp
 
-struct csp_ctx {
+namespace smcp {
+// What csp_set_partition builds (replaced as a whole by the next call): the level sets 1 / 2 (sets[0] is not used: the
+// lists of all cliques are DeviceCtx::lev2idx) and the tables of the boundary exchange
+struct PartitionTables {
+  LevelSet sets[3];
+  // boundary exchange of the subtree partition: the subtree roots of all ranks (device: clique, owning rank, offset in
+  // doubles per right-hand side inside the owner's region), what every rank contributes per right-hand side, the widest block
+  int32_t* xr_roots = nullptr; int32_t* xr_owner = nullptr; int64_t* xr_bptr = nullptr;
+  int64_t xr_n = 0; int xr_me = -1; int xr_world = 0; int64_t xr_npmax = 1;
+  std::vector<int64_t> xr_size;
+  bool fz_set1_ok = false;              // every family parent this rank owns has its parent front on this rank too
+  void release(DevLedger& mem) { dev_free(mem, sets[1].lev2, sets[2].lev2, xr_roots, xr_owner, xr_bptr); *this = PartitionTables(); }
+};
+}  // namespace smcp
+
+struct csp_ctx : smcp::PartitionTables {
   smcp::Symbolic S;
-  smcp::LevelSet sets[3];
   std::vector<smcp::LevelClass> lvl;
   smcp::DeviceCtx D;
   smcp::Profiler prof;
@@ -308,11 +330,6 @@ struct csp_ctx {
   std::vector<int64_t> fam;     // per clique: family role (CSP_Q_FAMILY)
   std::vector<uint8_t> is_diag_cache;
   std::vector<uint8_t> large_mask;   // per clique: a large (HBM-class) front
-  // boundary exchange of the subtree partition: the subtree roots of all ranks (device: clique, owning rank, offset in
-  // doubles per right-hand side inside the owner's region), what every rank contributes per right-hand side, the widest block
-  int32_t* xr_roots = nullptr; int32_t* xr_owner = nullptr; int64_t* xr_bptr = nullptr;
-  int64_t xr_n = 0; int xr_me = -1; int xr_world = 0; int64_t xr_npmax = 1;
-  std::vector<int64_t> xr_size;
   int64_t mrc_clamped = 0;              // cliques of the last csp_mrcompletion whose Schur factor lost columns to the r-column cap
   int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
@@ -323,13 +340,12 @@ struct csp_ctx {
   hipEvent_t aux_fork = nullptr, aux_join[2] = {nullptr, nullptr};
   int64_t scal_lstar = -1, scal_tail0 = 0;              // scaling_impl: first level without small cliques, start of the last level in blkval
   std::vector<uint8_t> fz_levels;       // per level: holds the parent front of some family parent (those levels' extend-add is the fused one)
-  bool fz_set1_ok = false;              // csp_set_partition: every family parent this rank owns has its parent front on this rank too
   bool fz_live = false; int fz_nat = 0, fz_cnn = 0; int64_t fz_recl = 0;   // the running sweep's family launch left the parents' updates to the extend-add above (k_lf_assemble_fz)
   bool plan_full_upd = false;           // the gather plans list every update-block position of the large fronts (no clear pass needed)
   bool lazy_status = false;             // csp_lazy_status: failure flags are latched on the device, read by csp_status
   // one-launch blocked Cholesky with in-launch tile dataflow (front_flow.hip): workspace per stream in use (caller's, side 0,
   // side 1: two such launches may run side by side) and the ownership plans by matrix order
-  struct FlowWs { double* P = nullptr; double* dinv = nullptr; unsigned* flags = nullptr; int cap_nt = 0, cap_fronts = 0; unsigned epoch = 0; };
+  struct FlowWs { double* P = nullptr; double* dinv = nullptr; unsigned* flags = nullptr; int64_t len_P = 0, len_dinv = 0, len_flags = 0; int cap_nt = 0, cap_fronts = 0; unsigned epoch = 0; };
   FlowWs flow_ws[3];
   struct FlowPlanDev { int nwg = 0; int32_t* own_ptr = nullptr; int32_t* own_tile = nullptr; };
   std::map<int, FlowPlanDev> flow_plans;     // key: order * 1024 + workgroups

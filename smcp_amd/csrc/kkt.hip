@@ -438,22 +438,8 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
   // a Schur complement of the OUTGOING constraint set still waiting for its factorisation (deferred status): it is complete
   // and does not depend on what is replaced here -- factor it where it stands, on the stream it was built on
   if (D.h_pending) { if (int rc = flush_pending_potrf(c, D.h_pending_stream, nullptr, false)) return rc; }
-  void* old[] = {D.fz_no, D.fz_slot, D.fz_ptr, D.fz_pk, D.fz_s, D.lg_eptr, D.lg_epk, D.lg_ew, D.lg_remap, D.lg_tab, D.cptr, D.cidx, D.cval, D.cwval, D.rpos, D.rptr, D.rcon, D.rval, D.ustack,
-                 D.a_r, D.a_c, D.s_rloc, D.s_cloc, D.dlist, D.slist, D.kidx, D.vbuf, D.hd, D.kc_ptr, D.kc_off, D.kc_val, D.kc_ij, D.scm_owner};
-  for (void* p : old) if (p) hipFree(p);
-  D.cptr = nullptr; D.cidx = nullptr; D.cval = nullptr; D.cwval = nullptr; D.rpos = nullptr;
-  D.rptr = nullptr; D.rcon = nullptr; D.rval = nullptr; D.ustack = nullptr;
-  D.a_r = D.a_c = D.s_rloc = D.s_cloc = D.dlist = D.slist = D.kidx = nullptr;
-  D.scm_owner = nullptr;
-  D.vbuf = D.hd = nullptr;
-  D.kc_ptr = D.kc_off = nullptr; D.kc_val = nullptr; D.kc_ij = nullptr;
-  D.fz_no = D.fz_slot = D.fz_ptr = D.fz_pk = nullptr; D.fz_s = nullptr; D.fz_nfam = 0; D.fz_ok = false;
-  D.md = D.ns = D.vcols = 0;
-  D.lg_children = 0; D.lg_nochild = false;
-  D.lg_eptr = D.lg_epk = D.lg_remap = nullptr; D.lg_ew = D.lg_tab = nullptr;
+  D.ConstraintBufs::release(D.mem);
   c->gsl_key.clear();
-  if (D.qr_ws) { hipFree(D.qr_ws); D.bytes -= D.qr_len * 8; D.qr_ws = nullptr; D.qr_len = 0; }
-  D.qr_valid = false;
   SetupClock clk("kkt_set_constraints");
   const int64_t nnz = cptr[m];
   // diagonal flags: position -> is it a diagonal entry of its NN block?
@@ -589,21 +575,21 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
   std::vector<int64_t> vcptr(cptr, cptr + m + 1), vcidx(cidx, cidx + nnz);
   std::vector<double> vcval(cval, cval + nnz);
   int rc = 0;
-  if ((rc = dev_upload(&D.cptr, vcptr, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.cidx, vcidx, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.cval, vcval, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.cwval, w, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.rpos, rpos, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.rptr, rptr, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.rcon, rcon, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.rval, rval, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.a_r, ar, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.a_c, ac, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.s_rloc, rloc, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.s_cloc, cloc, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.dlist, dl, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.slist, sl, D.bytes))) return rc;
-  if ((rc = dev_upload(&D.kidx, kidx, D.bytes))) return rc;
+  if ((rc = dev_upload(&D.cptr, vcptr, D.mem))) return rc;
+  if ((rc = dev_upload(&D.cidx, vcidx, D.mem))) return rc;
+  if ((rc = dev_upload(&D.cval, vcval, D.mem))) return rc;
+  if ((rc = dev_upload(&D.cwval, w, D.mem))) return rc;
+  if ((rc = dev_upload(&D.rpos, rpos, D.mem))) return rc;
+  if ((rc = dev_upload(&D.rptr, rptr, D.mem))) return rc;
+  if ((rc = dev_upload(&D.rcon, rcon, D.mem))) return rc;
+  if ((rc = dev_upload(&D.rval, rval, D.mem))) return rc;
+  if ((rc = dev_upload(&D.a_r, ar, D.mem))) return rc;
+  if ((rc = dev_upload(&D.a_c, ac, D.mem))) return rc;
+  if ((rc = dev_upload(&D.s_rloc, rloc, D.mem))) return rc;
+  if ((rc = dev_upload(&D.s_cloc, cloc, D.mem))) return rc;
+  if ((rc = dev_upload(&D.dlist, dl, D.mem))) return rc;
+  if ((rc = dev_upload(&D.slist, sl, D.mem))) return rc;
+  if ((rc = dev_upload(&D.kidx, kidx, D.mem))) return rc;
   clk.mark("uploads");
   D.md = (int64_t)dl.size();
   D.ns = (int64_t)sl.size();
@@ -614,8 +600,8 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
     const int64_t trsm_cap = std::max<int64_t>(1, (D.max_rhs * D.tmplen) / sepsum);
     const int64_t want = std::min<int64_t>((int64_t)kidx.size(), ((int64_t)256 << 20) / std::max<int64_t>(1, S.n * 8));
     D.vcols = std::min(trsm_cap, std::max(kmax, want));
-    if ((rc = dev_alloc(&D.vbuf, D.vcols * S.n, D.bytes))) return rc;
-    if (D.md && (rc = dev_alloc(&D.hd, D.md * D.md, D.bytes))) return rc;
+    if ((rc = dev_alloc(&D.vbuf, D.vcols * S.n, D.mem))) return rc;
+    if (D.md && (rc = dev_alloc(&D.hd, D.md * D.md, D.mem))) return rc;
   }
   // entries grouped by (clique, constraint): the sweeps of the Schur complement build their input panels from these
   if (nnz < ((int64_t)1 << 31) && S.nsn * (m + 1) <= ((int64_t)1 << 28)) {
@@ -727,11 +713,11 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
           }
       }
       for (size_t q = 0; q < dl.size(); ++q) remap[(size_t)dl[q]] = (int32_t)q;
-      if ((rc = dev_upload(&D.lg_eptr, lg_eptr, D.bytes))) return rc;
-      if ((rc = dev_upload(&D.lg_epk, epk, D.bytes))) return rc;
-      if ((rc = dev_upload(&D.lg_ew, ewv, D.bytes))) return rc;
-      if ((rc = dev_upload(&D.lg_remap, remap, D.bytes))) return rc;
-      if ((rc = dev_alloc(&D.lg_tab, D.lg_children * D.lg_rec, D.bytes))) return rc;
+      if ((rc = dev_upload(&D.lg_eptr, lg_eptr, D.mem))) return rc;
+      if ((rc = dev_upload(&D.lg_epk, epk, D.mem))) return rc;
+      if ((rc = dev_upload(&D.lg_ew, ewv, D.mem))) return rc;
+      if ((rc = dev_upload(&D.lg_remap, remap, D.mem))) return rc;
+      if ((rc = dev_alloc(&D.lg_tab, D.lg_children * D.lg_rec, D.mem))) return rc;
     }
     clk.mark("leaf Gram tables");
     // Static term lists of the family parents (fused extend-add, front_famt.hip lf_add_family): every entry of constraint j inside
@@ -800,32 +786,27 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
             }
           }
         });
-        if ((rc = dev_upload(&D.fz_no, fno, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.fz_ptr, fptr, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.fz_pk, fpk, D.bytes))) return rc;
-        if ((rc = dev_upload(&D.fz_s, fsv, D.bytes))) return rc;
-        if ((rc = dev_alloc(&D.fz_slot, nfam + 8, D.bytes))) return rc;      // (+ the eight task counters of k_lf_assemble_fz)
+        if ((rc = dev_upload(&D.fz_no, fno, D.mem))) return rc;
+        if ((rc = dev_upload(&D.fz_ptr, fptr, D.mem))) return rc;
+        if ((rc = dev_upload(&D.fz_pk, fpk, D.mem))) return rc;
+        if ((rc = dev_upload(&D.fz_s, fsv, D.mem))) return rc;
+        if ((rc = dev_alloc(&D.fz_slot, nfam + 8, D.mem))) return rc;      // (+ the eight task counters of k_lf_assemble_fz)
         HIPCHK(hipMemset(D.fz_slot, 0, sizeof(int32_t) * (nfam + 8)));
         D.fz_nfam = nfam;
         D.fz_ok = true;
       }
     }
     clk.mark("family term lists");
-    if ((rc = dev_upload(&D.kc_ij, kij, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.kc_ptr, kptr, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.kc_off, koff, D.bytes))) return rc;
-    if ((rc = dev_upload(&D.kc_val, kval, D.bytes))) return rc;
+    if ((rc = dev_upload(&D.kc_ij, kij, D.mem))) return rc;
+    if ((rc = dev_upload(&D.kc_ptr, kptr, D.mem))) return rc;
+    if ((rc = dev_upload(&D.kc_off, koff, D.mem))) return rc;
+    if ((rc = dev_upload(&D.kc_val, kval, D.mem))) return rc;
   }
   clk.mark("table uploads");
   D.ustack_cols = std::max(D.max_rhs, m);
-  if ((rc = dev_alloc(&D.ustack, D.ustack_cols * S.blklen(), D.bytes))) return rc;
+  if ((rc = dev_alloc(&D.ustack, D.ustack_cols * S.blklen(), D.mem))) return rc;
   // entries the sweeps never write (strict upper triangles of the NN blocks) must stay finite
   HIPCHK(hipMemset(D.ustack, 0, sizeof(double) * D.ustack_cols * S.blklen()));
-  if (!D.sw) {
-    if ((rc = dev_alloc(&D.sw, S.blklen(), D.bytes))) return rc;
-    hipLaunchKernelGGL(k_fill_sqrt_weights, dim3((unsigned)std::min<int64_t>(S.nsn, 4096)), dim3(256), 0, 0, D.cl, (int)S.nsn, D.sw);
-    HIPCHK(hipDeviceSynchronize());
-  }
   clk.mark("swept stack");
   D.m = m;
   D.cnnz = nnz;
@@ -868,12 +849,7 @@ static int potrf_launch(csp_ctx* c, double* A, int64_t n, int64_t lda, hipStream
   }
   if (n <= 2 * LB) {
     const int64_t need = 8 * 256 + 2 * n;
-    if (c->D.hinv_cap < need) {
-      if (c->D.hinv) { HIPCHK(hipFree(c->D.hinv)); c->D.bytes -= c->D.hinv_cap * 8; }
-      c->D.hinv = nullptr; c->D.hinv_cap = 0;
-      if (int rc = dev_alloc(&c->D.hinv, need, c->D.bytes)) return rc;
-      c->D.hinv_cap = need;
-    }
+    if (int rc = dev_grow(&c->D.hinv, &c->D.hinv_cap, need, c->D.mem, st)) return rc;
     const size_t lds = ((size_t)((n | 1) * n) + 256 + 8) * sizeof(double);
     static bool attr_set = false;
     if (!attr_set) {
@@ -892,12 +868,7 @@ static int potrf_launch(csp_ctx* c, double* A, int64_t n, int64_t lda, hipStream
   a.dn = (int)n; a.dld = lda;
   dim3 blk(256);
   const int64_t nblocks = (n + LB - 1) / LB, need = nblocks * LB * LB + 2 * n;
-  if (c->D.hinv_cap < need) {
-    if (c->D.hinv) { HIPCHK(hipFree(c->D.hinv)); c->D.bytes -= c->D.hinv_cap * 8; }
-    c->D.hinv = nullptr; c->D.hinv_cap = 0;
-    if (int rc = dev_alloc(&c->D.hinv, need, c->D.bytes)) return rc;
-    c->D.hinv_cap = need;
-  }
+  if (int rc = dev_grow(&c->D.hinv, &c->D.hinv_cap, need, c->D.mem, st)) return rc;
   // the whole blocked factorisation in ONE launch (front_flow.hip: tile dataflow inside the launch, the diagonal blocks' inverses
   // straight to their slots); SMCP_FLOW=0 or beyond 4096: three launches per block column
   if (flow_chol(c, st, A, lda, (int)n, c->D.hinv, nullptr, 5, info, 1)) return 0;
@@ -1050,17 +1021,11 @@ static int gram_count_chunks(const std::vector<std::pair<int64_t, int64_t>>& rs,
   for (auto& r : rs) n += (int)((r.second - r.first + chunk - 1) / chunk);
   return n;
 }
-static int gram_reserve(csp_ctx* c, int64_t m, int nchunk) {
+static int gram_reserve(csp_ctx* c, int64_t m, int nchunk, hipStream_t st) {
   DeviceCtx& D = c->D;
   const int nb = (int)((m + GRAM_BLK - 1) / GRAM_BLK), nblk = nb * (nb + 1) / 2;
   const int64_t need = (int64_t)nblk * nchunk * 64 * 256;
-  if (D.gpart_len < need) {
-    if (D.gpart) { HIPCHK(hipFree(D.gpart)); D.bytes -= D.gpart_len * 8; }
-    D.gpart = nullptr;
-    if (int rc = dev_alloc(&D.gpart, need, D.bytes)) return rc;
-    D.gpart_len = need;
-  }
-  return 0;
+  return dev_grow(&D.gpart, &D.gpart_len, need, D.mem, st);
 }
 // ---- slice table of a set of blkval ranges (k_gram_diag128) and the family children inside them (k_leaf_gram) ----------
 // Built on the host when the ranges (or the leaf switch) differ from the cached ones: a rank's ranges are the same at
@@ -1123,22 +1088,14 @@ static int gram_tables(csp_ctx* c, const std::vector<std::pair<int64_t, int64_t>
     start.insert(start.end(), late_start.begin(), late_start.end());
     len.insert(len.end(), late_len.begin(), late_len.end());
   }
-  auto grow = [&](auto** p, int64_t& cap, int64_t need) -> int {
-    if (cap >= need && *p) return 0;
-    if (*p) { if (hipFree(*p) != hipSuccess) return SMCP_EHIP; *p = nullptr; }
-    using T = typename std::remove_pointer<typename std::remove_pointer<decltype(p)>::type>::type;
-    T* q = nullptr;
-    if (hipMalloc((void**)&q, (size_t)std::max<int64_t>(need, 1) * sizeof(T)) != hipSuccess) return SMCP_ENOMEM;
-    *p = q; cap = need;
-    return 0;
-  };
+  // (two tables share each capacity; at least one element, so that a built table is never a null pointer)
+  const int64_t nslice = std::max<int64_t>((int64_t)start.size(), 1), nlist = std::max<int64_t>((int64_t)list.size(), 1);
+  int64_t cap_len = D.gsl_cap, cap_slot = D.lg_cap;
+  if (int rc = dev_grow(&D.gsl_start, &D.gsl_cap, nslice, D.mem, st)) return rc;
+  if (int rc = dev_grow(&D.gsl_len, &cap_len, nslice, D.mem, st)) return rc;
+  if (int rc = dev_grow(&D.lg_list, &D.lg_cap, nlist, D.mem, st)) return rc;
+  if (int rc = dev_grow(&D.lg_slot, &cap_slot, nlist, D.mem, st)) return rc;
   HIPCHK(hipStreamSynchronize(st));             // the tables may be in use by launches still queued
-  int64_t cap_len = D.gsl_cap;
-  if (int rc = grow(&D.gsl_start, D.gsl_cap, (int64_t)start.size())) return rc;
-  if (int rc = grow(&D.gsl_len, cap_len, (int64_t)start.size())) return rc;
-  int64_t cap_slot = D.lg_cap;
-  if (int rc = grow(&D.lg_list, D.lg_cap, (int64_t)list.size())) return rc;
-  if (int rc = grow(&D.lg_slot, cap_slot, (int64_t)list.size())) return rc;
   if (!start.empty()) {
     HIPCHK(hipMemcpy(D.gsl_start, start.data(), start.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(D.gsl_len, len.data(), len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -1271,7 +1228,7 @@ static int gram_accumulate(csp_ctx* c, int64_t nranges, const int64_t* ranges, d
       spw = (int)(chunk / GRAM_KS);
       nchunk = std::max(1, (D.gsl_n + spw - 1) / spw);
       ngram = D.gsl_n > 0 ? nchunk : 0;
-      if (int rc = gram_reserve(c, m, nchunk + (leaf ? leafgram_slots(c) : 0) + GRAM_RZ)) return rc;
+      if (int rc = gram_reserve(c, m, nchunk + (leaf ? leafgram_slots(c) : 0) + GRAM_RZ, st)) return rc;
       if (leaf) { if (int rc = leafgram_partials(c, m, ids, st, D.gpart + (int64_t)ngram * (64 * 256), &nl)) return rc; }
     }
     c->gpre.valid = false; c->gpre.early_done = false;
@@ -1303,7 +1260,7 @@ static int gram_accumulate(csp_ctx* c, int64_t nranges, const int64_t* ranges, d
   if (leaf) return SMCP_EINVAL;                 // leafgram_ok admits one block only
   const int64_t chunk = gram_chunk_rows(total);
   const int nchunk = gram_count_chunks(rs, chunk);
-  if (int rc = gram_reserve(c, m, nchunk)) return rc;
+  if (int rc = gram_reserve(c, m, nchunk, st)) return rc;
   int coff = 0;
   for (auto& r : rs) {
     const int64_t lo = r.first, hi = r.second;
@@ -1370,7 +1327,7 @@ static int schur_gram(csp_ctx* c, const double* L, const double* Y, double* H, i
         const int spw = D.gsl_spw ? D.gsl_spw : (int)(chunk / GRAM_KS);
         const int nchunk = std::max(1, (D.gsl_n + spw - 1) / spw);
         const int ngram = D.gsl_n > 0 ? nchunk : 0;
-        if (gram_reserve(c, m, nchunk + leafgram_slots(c) + GRAM_RZ)) return;
+        if (gram_reserve(c, m, nchunk + leafgram_slots(c) + GRAM_RZ, side)) return;
         int nl = 0;
         if (leafgram_partials(c, m, nullptr, side, D.gpart + (int64_t)ngram * (64 * 256), &nl)) return;
         c->gpre.valid = true; c->gpre.ngram = ngram; c->gpre.nchunk = nchunk; c->gpre.spw = spw; c->gpre.nl = nl;
@@ -1417,7 +1374,7 @@ static int schur_gram(csp_ctx* c, const double* L, const double* Y, double* H, i
     std::vector<int32_t> ow((size_t)m, -1);
     for (int64_t p = 0; p < nparts; ++p)
       for (int64_t q = D.ns * p / nparts; q < D.ns * (p + 1) / nparts; ++q) ow[(size_t)c->h_slist[(size_t)q]] = (int32_t)p;
-    if (!D.scm_owner) { if (int rc = dev_alloc(&D.scm_owner, m, D.bytes)) return rc; }
+    if (!D.scm_owner) { if (int rc = dev_alloc(&D.scm_owner, m, D.mem)) return rc; }
     HIPCHK(hipMemcpyAsync(D.scm_owner, ow.data(), sizeof(int32_t) * m, hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st));      // ow is a local
     owner = D.scm_owner;
@@ -1627,13 +1584,13 @@ int csp_set_partition(csp_ctx* c, const int32_t* owner, int rank) {
   if (int rc = ready(c)) return rc;
   const Symbolic& S = c->S;
   HIPCHK(hipSetDevice(c->D.device));
+  c->PartitionTables::release(c->D.mem);
   for (int set = 1; set <= 2; ++set) {
     LevelSet& LS = c->sets[set];
-    if (LS.lev2) { HIPCHK(hipFree(LS.lev2)); LS.lev2 = nullptr; }
     std::vector<int32_t> lev2;
     const int want = (set == 1) ? rank : -1;
     classify_levels(S, [&](int64_t k) { return owner[k] == want; }, LS.lvl, lev2, LS.off);
-    if (int rc = dev_upload(&LS.lev2, lev2, c->D.bytes)) return rc;
+    if (int rc = dev_upload(&LS.lev2, lev2, c->D.mem)) return rc;
   }
   // subtree roots (owned clique whose parent lies in the replicated top), rank by rank in ascending clique order
   int world = 0;
@@ -1650,17 +1607,15 @@ int csp_set_partition(csp_ctx* c, const int32_t* owner, int rank) {
         c->xr_size[r] += np;
         c->xr_npmax = std::max(c->xr_npmax, np);
       }
-  for (void* p : {(void*)c->xr_roots, (void*)c->xr_owner, (void*)c->xr_bptr}) if (p) HIPCHK(hipFree(p));
-  c->xr_roots = nullptr; c->xr_owner = nullptr; c->xr_bptr = nullptr;
   c->xr_n = (int64_t)roots.size(); c->xr_me = rank; c->xr_world = world;
   // may the owned sweeps leave the family parents' updates to the extend-add above (fz_on)?  Only when no family parent of this
   // rank is a subtree root: a root's update is what the boundary exchange packs, so it has to exist in the exchange buffer
   c->fz_set1_ok = true;
   for (int64_t k = 0; k < S.nsn; ++k)
     if (k < (int64_t)c->fam.size() && c->fam[(size_t)k] == 2 && owner[k] == rank && (S.snpar[k] < 0 || owner[S.snpar[k]] != rank)) c->fz_set1_ok = false;
-  if (int rc = dev_upload(&c->xr_roots, roots, c->D.bytes)) return rc;
-  if (int rc = dev_upload(&c->xr_owner, own, c->D.bytes)) return rc;
-  if (int rc = dev_upload(&c->xr_bptr, bptr, c->D.bytes)) return rc;
+  if (int rc = dev_upload(&c->xr_roots, roots, c->D.mem)) return rc;
+  if (int rc = dev_upload(&c->xr_owner, own, c->D.mem)) return rc;
+  if (int rc = dev_upload(&c->xr_bptr, bptr, c->D.mem)) return rc;
   return 0;
 }
 int kkt_gram_prepare(csp_ctx* c, const double* L, const double* Y, void* stream) {

@@ -240,7 +240,7 @@ int potrs_many_impl(csp_ctx* c, const double* A, int64_t n, int64_t lda, double*
     return 0;
   }
   // the forward solution lives in the scratch image of csp_trsm / csp_trmm (no call keeps it): n x nrhs, leading dimension n
-  if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, n * nrhs, D.bytes, st)) return rc;
+  if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, n * nrhs, D.mem, st)) return rc;
   double* const Yw = D.trsm_x;
   // the updates of the other rows: FMA below eight columns of a workgroup's block, tile products on the matrix cores from eight on
   // (the gate of csp_trmm / csp_symm); SMCP_POTRS_MANY_MM=0: FMA only.  Read on every call: tools/solve_many_time.py alternates the two

@@ -397,8 +397,8 @@ int qr_alloc(csp_ctx* c) {
   // G | T | Lc | scratch (m x m each), Rp (ldr x ldr: the packed factor of the pass), r1 (bl), part (m * nchunk), xm, r2 (m each)
   const int64_t need = 4 * m * m + ldr * ldr + bl + m * nchunk + 2 * m + bl;     // ... and the weighted copy of r1 at the end
   if (D.qr_ws && D.qr_len >= need) return 0;
-  if (D.qr_ws) { HIPCHK(hipFree(D.qr_ws)); D.bytes -= D.qr_len * 8; D.qr_ws = nullptr; }
-  if (int rc = dev_alloc(&D.qr_ws, need, D.bytes)) return rc;
+  if (dev_free(D.mem, D.qr_ws)) return SMCP_EHIP;
+  if (int rc = dev_alloc(&D.qr_ws, need, D.mem)) return rc;
   D.qr_len = need;
   HIPCHK(hipMemset(D.qr_ws, 0, sizeof(double) * need));
   return 0;

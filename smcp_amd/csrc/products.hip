@@ -20,7 +20,7 @@ std::vector<int64_t> large_fronts_first(const csp_ctx* c) {
 // f(row, slot) once per contribution IN THE ORDER OF THE ROW SUMS of the combine kernel: the contribution stored by its
 // producer at `slot` gets the next position of `row`.  That order decides the bits of the results.
 template <class Each>
-int build_row_index(RowIndex* R, int64_t n, int64_t ntot, int heavy_from, Each each, int64_t& bytes) {
+int build_row_index(RowIndex* R, int64_t n, int64_t ntot, int heavy_from, Each each, DevLedger& mem) {
   std::vector<int64_t> tptr((size_t)n + 1, 0);
   each([&](int64_t row, int64_t) { ++tptr[(size_t)row + 1]; });
   for (int64_t i = 0; i < n; ++i) tptr[(size_t)i + 1] += tptr[(size_t)i];
@@ -32,9 +32,9 @@ int build_row_index(RowIndex* R, int64_t n, int64_t ntot, int heavy_from, Each e
   std::vector<int32_t> heavy;
   for (int64_t i = 0; i < n; ++i) if (tptr[(size_t)i + 1] - tptr[(size_t)i] > heavy_from) heavy.push_back((int32_t)i);
   R->nheavy = (int64_t)heavy.size();
-  if (int rc = dev_upload(&R->pos, pos, bytes)) return rc;
-  if (int rc = dev_upload(&R->heavy, heavy, bytes)) return rc;
-  return dev_upload(&R->tptr, tptr, bytes);      // last: tptr marks the index (and its owner's plan) as built
+  if (int rc = dev_upload(&R->pos, pos, mem)) return rc;
+  if (int rc = dev_upload(&R->heavy, heavy, mem)) return rc;
+  return dev_upload(&R->tptr, tptr, mem);      // last: tptr marks the index (and its owner's plan) as built
 }
 
 // Which kernels take the fronts of a product: the FMA kernels only, tile products for the large fronts, or tile products
@@ -111,10 +111,10 @@ int trmm_setup(csp_ctx* c) {
     }
   }
   for (int t = 0; t < 2; ++t) {
-    if (int rc = dev_upload(&P.tiles[t], tiles[t], D.bytes)) return rc;
+    if (int rc = dev_upload(&P.tiles[t], tiles[t], D.mem)) return rc;
     P.ntiles[t][0] = nlarge[t];
     P.ntiles[t][1] = (int64_t)tiles[t].size() / 2;
-    if (int rc = dev_upload(&P.items[t], items[t], D.bytes)) return rc;
+    if (int rc = dev_upload(&P.items[t], items[t], D.mem)) return rc;
     P.nitems[t][0] = nsmall[t];
     P.nitems[t][1] = (int64_t)items[t].size() / 2;
   }
@@ -122,7 +122,7 @@ int trmm_setup(csp_ctx* c) {
     for (int64_t k = 0; k < S.nsn; ++k)
       for (int64_t q = 0; q < S.na(k); ++q) f(S.rowidx[S.rowptr[k] + S.nn(k) + q], S.sepptr[k] + q);
   };
-  return build_row_index(&P.idx, S.n, S.sepptr[S.nsn], TRMM_HEAVY, each, D.bytes);
+  return build_row_index(&P.idx, S.n, S.sepptr[S.nsn], TRMM_HEAVY, each, D.mem);
 }
 
 // ---- rank-k updates projected on the pattern (front_syr2k.hip) ------------------------------------------------------
@@ -153,8 +153,8 @@ int syr2k_setup(csp_ctx* c) {
   }
   P.ntiles[1] = (int64_t)tiles.size() / 4;
   if (P.nitems[1] >= ((int64_t)1 << 31) || P.ntiles[1] >= ((int64_t)1 << 31)) return SMCP_EINVAL;     // grid dimension
-  if (int rc = dev_upload(&P.items, items, D.bytes)) return rc;
-  if (int rc = dev_upload(&P.tiles, tiles, D.bytes)) return rc;
+  if (int rc = dev_upload(&P.items, items, D.mem)) return rc;
+  if (int rc = dev_upload(&P.tiles, tiles, D.mem)) return rc;
   P.ready = true;
   return 0;
 }
@@ -209,7 +209,7 @@ int symm_setup(csp_ctx* c) {
     if ((int64_t)x + 1 == D.nII_total) P.nitems[0] = (int64_t)items.size() / 4;
   }
   P.nitems[1] = (int64_t)items.size() / 4;
-  if (int rc = dev_upload(&P.items, items, D.bytes)) return rc;
+  if (int rc = dev_upload(&P.items, items, D.mem)) return rc;
   auto each = [&](auto f) {                       // ascending (k, side, r, p): the order of the sums of k_symm_combine
     int64_t nrows, ncol;
     for (int64_t k = 0; k < S.nsn; ++k)
@@ -221,7 +221,7 @@ int symm_setup(csp_ctx* c) {
           else for (int64_t j = 0; j < ncol; ++j) f(S.snptr[k] + p * SYMM_KP + j, base + nrows + j);
         }
   };
-  return build_row_index(&P.idx, S.n, ntot, SYMM_HEAVY, each, D.bytes);
+  return build_row_index(&P.idx, S.n, ntot, SYMM_HEAVY, each, D.mem);
 }
 
 }  // namespace
@@ -241,7 +241,7 @@ int csp_trmm(csp_ctx* c, const double* L, double* B, int64_t nrhs, int64_t ldb, 
   if (int rc = trmm_setup(c)) return rc;
   if (!trans && S.sepptr[S.nsn] * nrhs > D.max_rhs * D.tmplen) return SMCP_ENOMEM;
   // the scratch image of B is csp_trsm's: neither call keeps it
-  if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, ldb * nrhs, D.bytes, st)) return rc;
+  if (int rc = dev_grow(&D.trsm_x, &D.trsm_x_len, ldb * nrhs, D.mem, st)) return rc;
   // tile products: the large fronts from eight columns on (the gate of csp_trsm), every front from TRMM_MM_ALL on
   const Route route = product_route(c, mm, nrhs, 8, TRMM_MM_ALL, D.nII_total > 0, false);
   TrmmArgs a;

@@ -5,7 +5,9 @@
 * ldu, ldb and ldh may exceed the packed size and the padding is never written;
 * more right-hand sides than the context's max_rhs (ragged last chunks of one);
 * the caller's stream: work queued on a non-default stream behind a long-running producer, no host synchronisation;
-* NaN / Inf in the input of a factorisation is a failure (ArithmeticError), not a result, and the context recovers.
+* NaN / Inf in the input of a factorisation is a failure (ArithmeticError), not a result, and the context recovers;
+* csp_device_bytes is what the context holds NOW: replacing the constraints, repeating a partition and growing max_rhs
+  give back what they replace (exact integer equalities on fresh contexts).
 
 Bounds are those of tests/test_gpu_dense_ref.py (dense_ref.device_bound).
 """
@@ -16,13 +18,14 @@ import pytest
 import torch
 
 from oracle import oracle as orc
-from smcp_amd import _lib, chordal
+from smcp_amd import _lib, chordal, problems, shard
 from smcp_amd.cspmatrix import _stream, cspmatrix
 from smcp_amd.kkt import KKTSystem
 from smcp_amd.symbolic import Symbolic
 from tests import dense_ref
 from tests.dense_ref import HESS_MODES, MODE_OP, blockwise, relvec, to_dev, to_host
 from tests.helpers import GPU_PATTERNS
+from tests.test_gpu_parity import setup
 
 pytestmark = pytest.mark.gpu
 NAMES = sorted(GPU_PATTERNS)
@@ -364,3 +367,60 @@ def test_nan_and_inf_in_the_input_are_failures(name, kind, value, where, cases, 
     chordal.cholesky_projected_inverse(L, Y)
     assert blockwise(S, to_host(L), case.cholesky())[1] <= dense_ref.device_bound("cholesky", yard)
     assert blockwise(S, to_host(Y), case.Yblk)[1] <= dense_ref.device_bound("projected_inverse", yard)
+
+
+# ---- device memory ------------------------------------------------------------------------------------------------------
+def _bytes_after_solves(name, ms):
+    """A fresh context (device_init(0, 4)); per m of ms a KKTSystem on random_constraints(symb, m, density=0.05, seed=9) and
+    one factor + solve of the Cholesky solver; device_bytes() after each."""
+    symb, _, A, msk = setup(name, 7)
+    L = to_dev(symb, A)
+    chordal.cholesky(L)
+    Y = L.copy()
+    chordal.projected_inverse(Y)
+    rng = np.random.default_rng(2)
+    out = []
+    for m in ms:
+        sys_ = KKTSystem(symb, *problems.random_constraints(symb, m, density=0.05, seed=9), max_rhs=4)
+        solve = sys_.factor(L, Y)
+        solve(to_dev(symb, rng.standard_normal(symb.blklen) * msk), cuda(rng.standard_normal(m)), 1.0)
+        torch.cuda.synchronize()
+        out.append(symb.device_bytes())
+    return out
+
+
+@pytest.mark.parametrize("name", ["fam_odd", "arrow_big", "dense600"])
+def test_replacing_constraints_returns_the_memory(name):
+    b1, b2, b3 = _bytes_after_solves(name, (7, 3, 7))
+    print("device bytes after m = 7, 3, 7:", b1, b2, b3)
+    assert b3 == b1
+    # (the first context is gone by now: nothing of it may count for the second)
+    assert _bytes_after_solves(name, (7,)) == [b1]
+
+
+def test_repeating_a_partition_returns_the_memory():
+    symb = Symbolic(GPU_PATTERNS["nested_mid"]())
+    symb.device_init(0, 4)
+    owner = np.ascontiguousarray(shard.subtree_partition(symb, 2).owner, dtype=np.int32)
+    assert owner.max() == 1
+    lib = _lib.lib()
+    assert lib.csp_set_partition(symb.handle, owner.ctypes.data, 0) == 0
+    b1 = symb.device_bytes()
+    assert lib.csp_set_partition(symb.handle, owner.ctypes.data, 0) == 0
+    b2 = symb.device_bytes()
+    print("device bytes after the first and the second csp_set_partition:", b1, b2)
+    assert b2 == b1
+
+
+def test_growing_max_rhs_replaces_the_workspaces():
+    pat = GPU_PATTERNS["fam_odd"]()
+    grown = Symbolic(pat)
+    grown.device_init(0, 4)
+    b4 = grown.device_bytes()
+    grown.device_init(0, 9)
+    direct = Symbolic(pat)
+    direct.device_init(0, 9)
+    print("device bytes at max_rhs 4, grown to 9, 9 at once:", b4, grown.device_bytes(), direct.device_bytes())
+    assert grown.device_bytes() == direct.device_bytes() > b4
+    grown.device_init(0, 4)
+    assert grown.device_bytes() == direct.device_bytes()
