@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsmcp_amd.so")
-SOURCES = ["capi.hip", "symbolic.cpp"]
+SOURCES = ["capi.hip", "symbolic.cpp", "constraints.cpp"]
 
 
 def _stale():

@@ -16,7 +16,9 @@
 #include <vector>
 
 #include "../../include/smcp_amd.h"
+#include "constraints.hpp"
 #include "context.hpp"
+#include "hostpar.hpp"
 #include "switches.hpp"
 #include "front_generic.hip"
 #include "front_mfma.hip"
@@ -268,21 +270,6 @@ inline void launch(csp_ctx* c, int kid, K kern, dim3 grid, dim3 block, hipStream
     (void)hipEventRecord(P.next(), st);
     P.kids.push_back(kid);
   }
-}
-
-// host worker threads for the set-up phases: work(tix) for tix = 0 .. nth - 1.  Thread creation can fail
-// (std::system_error); nothing may propagate across the extern "C" boundary, so whatever did not start runs inline.
-template <class F>
-void run_threads(int nth, F work) {
-  if (nth <= 1) { work(0); return; }
-  std::vector<std::thread> pool;
-  int started = 0;
-  try {
-    for (; started < nth; ++started) pool.emplace_back(work, started);
-  } catch (...) {
-  }
-  for (int tix = started; tix < nth; ++tix) work(tix);
-  for (auto& th : pool) th.join();
 }
 
 TreeArgs tree_args(csp_ctx* c) {
@@ -1209,10 +1196,11 @@ inline bool famt_disabled() {
 // chunk of the descriptor area), so ONE long list -- a multiple of the identity among sparse constraints: 15 + 8 x 5 diagonal
 // entries per family -- sent the whole set to the dense route (1.86 x the step).  Now the kernels take long lists in chunks
 // (FAMT_TMAX) and the gate is the mean.  SMCP_FAMT_MEAN moves it.
-inline bool famt_terms_ok(const DeviceCtx& D) {
+inline bool famt_terms_ok(int64_t fam_maxterms, double fam_meanterms) {
   static const int gate = sw_int("SMCP_FAMT_MEAN", 36);
-  return D.fam_maxterms <= FAMT_TMAX && D.fam_meanterms <= (double)gate;
+  return fam_maxterms <= FAMT_TMAX && fam_meanterms <= (double)gate;
 }
+inline bool famt_terms_ok(const DeviceCtx& D) { return famt_terms_ok(D.fam_maxterms, D.fam_meanterms); }
 // LDS of the grouped kernel: entries it can stage (< 0: the fixed part does not fit); one pass of a group needs at most
 // FAMT_GMAX x FAMT_TCAP / 2 of them
 template <int NAT>

@@ -55,12 +55,15 @@ inline void dev_free_all(DevLedger& mem) {
 }
 
 template <class T>
-int dev_upload(T** dst, const std::vector<T>& src, DevLedger& mem) {
-  size_t n = std::max<size_t>(src.size(), 1) * sizeof(T);
+int dev_upload(T** dst, const T* src, size_t count, DevLedger& mem) {
+  size_t n = std::max<size_t>(count, 1) * sizeof(T);
   if (dev_malloc(mem, (void**)dst, n) != hipSuccess) return SMCP_ENOMEM;
-  if (!src.empty() && hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
-    return SMCP_EHIP;
+  if (count && hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return SMCP_EHIP;
   return 0;
+}
+template <class T>
+int dev_upload(T** dst, const std::vector<T>& src, DevLedger& mem) {
+  return dev_upload(dst, src.data(), src.size(), mem);
 }
 template <class T>
 int dev_alloc(T** dst, int64_t count, DevLedger& mem) {

@@ -425,6 +425,46 @@ int aadj_impl(csp_ctx* c, const double* y, double* X, hipStream_t st) {
   return 0;
 }
 
+// Uploads and allocations of a built constraint set.  Their order is part of the contract: the placement of the large
+// buffers (ustack last) is what the measured step times were taken with.
+int upload_constraint_tables(csp_ctx* c, const ConstraintTables& T, int64_t m, const int64_t* cptr, const int64_t* cidx,
+                             const double* cval, SetupClock& clk) {
+  DeviceCtx& D = c->D;
+  const int64_t nnz = cptr[m], blklen = c->S.blklen();
+  int rc = 0;                    // the first failure; nothing is uploaded or allocated after it
+  auto up = [&](auto** dst, const auto& src) { if (!rc) rc = dev_upload(dst, src, D.mem); };
+  auto upn = [&](auto** dst, const auto* src, int64_t n) { if (!rc) rc = dev_upload(dst, src, (size_t)n, D.mem); };
+  auto alloc = [&](auto** dst, int64_t n) { if (!rc) rc = dev_alloc(dst, n, D.mem); };
+  upn(&D.cptr, cptr, m + 1); upn(&D.cidx, cidx, nnz); upn(&D.cval, cval, nnz);
+  up(&D.cwval, T.w);
+  up(&D.rpos, T.rpos); up(&D.rptr, T.rptr); up(&D.rcon, T.rcon); up(&D.rval, T.rval);
+  up(&D.a_r, T.ar); up(&D.a_c, T.ac); up(&D.s_rloc, T.rloc); up(&D.s_cloc, T.cloc);
+  up(&D.dlist, T.dl); up(&D.slist, T.sl); up(&D.kidx, T.kidx);
+  if (!T.sl.empty()) {
+    alloc(&D.vbuf, T.vcols * c->S.n);
+    if (!T.dl.empty()) alloc(&D.hd, (int64_t)(T.dl.size() * T.dl.size()));
+  }
+  if (T.has_leafgram) {
+    up(&D.lg_eptr, T.lg_eptr); up(&D.lg_epk, T.epk); up(&D.lg_ew, T.ewv); up(&D.lg_remap, T.remap);
+    alloc(&D.lg_tab, T.lg_children * T.lg_rec);
+  }
+  if (T.has_fam_terms) {
+    up(&D.fz_no, T.fno); up(&D.fz_ptr, T.fptr); up(&D.fz_pk, T.fpk); up(&D.fz_s, T.fsv);
+    alloc(&D.fz_slot, T.fz_nfam + 8);                                  // (+ the eight task counters of k_lf_assemble_fz)
+    if (rc) return rc;
+    HIPCHK(hipMemset(D.fz_slot, 0, sizeof(int32_t) * (T.fz_nfam + 8)));
+  }
+  if (T.has_entry_tables) { up(&D.kc_ij, T.kij); up(&D.kc_ptr, T.kptr); up(&D.kc_off, T.koff); up(&D.kc_val, T.kval); }
+  if (rc) return rc;
+  clk.mark("uploads");
+  const int64_t ustack_cols = std::max(D.max_rhs, m);
+  if ((rc = dev_alloc(&D.ustack, ustack_cols * blklen, D.mem))) return rc;
+  // entries the sweeps never write (strict upper triangles of the NN blocks) must stay finite
+  HIPCHK(hipMemset(D.ustack, 0, sizeof(double) * ustack_cols * blklen));
+  clk.mark("swept stack");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -433,7 +473,6 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
   if (int rc = ready(c)) return rc;
   if (m < 1 || !cptr || !cidx || !cval) return SMCP_EINVAL;
   DeviceCtx& D = c->D;
-  const Symbolic& S = c->S;
   HIPCHK(hipSetDevice(D.device));
   // a Schur complement of the OUTGOING constraint set still waiting for its factorisation (deferred status): it is complete
   // and does not depend on what is replaced here -- factor it where it stands, on the stream it was built on
@@ -441,376 +480,42 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
   D.ConstraintBufs::release(D.mem);
   c->gsl_key.clear();
   SetupClock clk("kkt_set_constraints");
-  const int64_t nnz = cptr[m];
-  // diagonal flags: position -> is it a diagonal entry of its NN block?
-  std::vector<double> w(nnz);
-  std::vector<int32_t> ar(nnz), ac(nnz);   // entries in (permuted) matrix coordinates
-  std::vector<int32_t> ek(nnz), eoff(nnz); // clique of each entry, position inside that clique's panel
-  {
-    // locate clique by binary search on blkptr (the entry ranges split over host threads)
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), (int64_t)16, nnz / 65536 + 1}));
-    std::atomic<int> bad{0};
-    auto work = [&](int tix) {
-      const int64_t e0 = nnz * tix / nth, e1 = nnz * (tix + 1) / nth;
-      int64_t k = 0;
-      for (int64_t e = e0; e < e1; ++e) {
-        int64_t pos = cidx[e];
-        if (pos < 0 || pos >= S.blklen()) { bad = 1; return; }
-        if (pos < S.blkptr[k] || pos >= S.blkptr[k + 1])      // (runs of entries share their clique)
-          k = (int64_t)(std::upper_bound(S.blkptr.begin(), S.blkptr.end(), pos) - S.blkptr.begin()) - 1;
-        int64_t nf = S.nf(k), off = pos - S.blkptr[k];
-        int64_t col = off / nf, row = off % nf;
-        if (row < col) { bad = 1; return; }  // upper triangle of the NN block is not part of V
-        w[e] = (row == col) ? cval[e] : 2.0 * cval[e];
-        ar[e] = (int32_t)S.rowidx[S.rowptr[k] + row];
-        ac[e] = (int32_t)(S.snptr[k] + col);
-        ek[e] = (int32_t)k;
-        eoff[e] = (int32_t)off;
-      }
-    };
-    run_threads(nth, work);
-    if (bad) return SMCP_EINVAL;
+  static int scm_off = -1;
+  if (scm_off < 0) { const char* e = sw_str("SMCP_SCM"); scm_off = (e && e[0] == '0') ? 1 : 0; }
+  ConstraintParams P;
+  P.tnzcols = c->tnzcols;
+  P.max_rhs = D.max_rhs;
+  P.tmplen = D.tmplen;
+  P.scm_on = !scm_off && !use_generic(c);
+  P.fam = &c->fam;
+  P.large_mask = &c->large_mask;
+  P.famt_terms_ok = famt_terms_ok;
+  P.lf_alds_maxnf = LF_ALDS_MAXNF;
+  P.famt_child = FAMT_CHILD;
+  // every host table first (constraints.cpp; an invalid entry leaves the context without constraints, its host lists untouched)
+  ConstraintTables T;
+  if (int rc = build_constraint_tables(c->S, P, m, cptr, cidx, cval, T, [&](const char* step, int) { clk.mark(step); })) return rc;
+  c->h_kptr = std::move(T.h_kptr);
+  c->h_slist = T.sl;
+  if (int rc = upload_constraint_tables(c, T, m, cptr, cidx, cval, clk)) return rc;
+  D.md = (int64_t)T.dl.size();
+  D.ns = (int64_t)T.sl.size();
+  if (D.ns) D.vcols = T.vcols;
+  if (T.has_entry_tables) {
+    D.kc_maxlist = T.kc_maxlist;
+    D.fam_maxterms = T.fam_maxterms;
+    D.fam_meanterms = T.fam_meanterms;
+    D.kc_maxlist_large = T.kc_maxlist_large;
+    D.kc_sorted = T.kc_sorted;
+    D.lg_children = T.lg_children; D.lg_maxent = T.lg_maxent; D.lg_pairs = T.lg_pairs; D.lg_rows = T.lg_rows; D.lg_rec = T.lg_rec;
+    c->lg_slot_of = std::move(T.lg_slot_of);
   }
-  clk.mark("locate entries");
-  // Column-sparse constraints (misc.nzcolumns / misc.matperm, misc.c:682-773, solvers.py:246-268): a constraint
-  // whose entries touch at most int(n * tnzcols) distinct rows/columns takes the SCMcolumn2 path (two sparse
-  // triangular solves for S^-1[:, K_s], then pairwise contractions) instead of a Hessian sweep.
-  std::vector<int32_t> dl, sl, kidx, rloc(nnz, 0), cloc(nnz, 0);
-  c->h_kptr.assign(1, 0);
-  {
-    static int off = -1;
-    if (off < 0) { const char* e = sw_str("SMCP_SCM"); off = (e && e[0] == '0') ? 1 : 0; }
-    const int64_t tnz = (int64_t)((double)S.n * c->tnzcols);
-    // at most this many columns of S^-1 are formed per constraint (n x |K| doubles of workspace)
-    const int64_t kcap = std::min<int64_t>(tnz, std::max<int64_t>(1, ((int64_t)256 << 20) / std::max<int64_t>(1, S.n * 8)));
-    const int64_t sepsum = std::max<int64_t>(1, S.sepptr[S.nsn]);
-    const int64_t trsm_cap = std::max<int64_t>(1, (D.max_rhs * D.tmplen) / sepsum);
-    // the distinct rows / columns of every constraint: independent per constraint, host threads take them round-robin
-    // (synth50k: 100 sorts of 23 k indices, 65 ms on one thread); the lists are then joined in constraint order
-    std::vector<std::vector<int32_t>> kss((size_t)m);
-    std::vector<char> is_sparse((size_t)m, 0);
-    const bool scm_on = !off && !use_generic(c);
-    const int64_t cap = std::min(kcap, trsm_cap);
-    {
-      const unsigned hw = std::thread::hardware_concurrency();
-      const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), (int64_t)16, m, nnz / 4096 + 1}));
-      auto work = [&](int tix) {
-        for (int64_t j = tix; j < m; j += nth) {
-          std::vector<int32_t>& ks = kss[(size_t)j];
-          ks.reserve((size_t)(2 * (cptr[j + 1] - cptr[j])));
-          for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) { ks.push_back(ar[e]); ks.push_back(ac[e]); }
-          std::sort(ks.begin(), ks.end());
-          ks.erase(std::unique(ks.begin(), ks.end()), ks.end());
-          const int64_t nz = (int64_t)ks.size();
-          const bool sparse = scm_on && nz > 0 && nz <= cap;
-          is_sparse[(size_t)j] = sparse ? 1 : 0;
-          if (!sparse) { std::vector<int32_t>().swap(ks); continue; }
-          for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) {
-            rloc[e] = (int32_t)(std::lower_bound(ks.begin(), ks.end(), ar[e]) - ks.begin());
-            cloc[e] = (int32_t)(std::lower_bound(ks.begin(), ks.end(), ac[e]) - ks.begin());
-          }
-        }
-      };
-      run_threads(nth, work);
-    }
-    for (int64_t j = 0; j < m; ++j) {
-      if (!is_sparse[(size_t)j]) { dl.push_back((int32_t)j); continue; }
-      sl.push_back((int32_t)j);
-      kidx.insert(kidx.end(), kss[(size_t)j].begin(), kss[(size_t)j].end());
-      c->h_kptr.push_back((int64_t)kidx.size());
-    }
-  }
-  c->h_slist = sl;
-  clk.mark("classify");
-  // CSR by position
-  // entries ordered by position, ties in constraint order: a counting sort over the positions of V (a comparison sort
-  // of the 1.1 M entries of synth50k took 74 ms)
-  // ... split by position range over host threads: every thread walks the entry list for the positions of its range
-  // (counts, then places), so the pieces come out in global order and only their offsets are laid out serially
-  std::vector<int64_t> rpos, rptr;
-  std::vector<int32_t> rcon(nnz);
-  std::vector<double> rval(nnz);
-  {
-    std::vector<int32_t> con(nnz);
-    for (int64_t j = 0; j < m; ++j)
-      for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) con[e] = (int32_t)j;
-    const unsigned hw = std::thread::hardware_concurrency();
-    const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), (int64_t)16, nnz / 65536 + 1}));
-    const int64_t P = S.blklen();
-    std::vector<std::vector<int64_t>> start((size_t)nth);          // per thread: first slot of every position of its range
-    std::vector<int64_t> ecount((size_t)nth + 1, 0), dcount((size_t)nth + 1, 0);
-    auto count = [&](int tix) {
-      const int64_t p0 = P * tix / nth, p1 = P * (tix + 1) / nth;
-      std::vector<int64_t>& st = start[(size_t)tix];
-      st.assign((size_t)(p1 - p0) + 1, 0);
-      for (int64_t e = 0; e < nnz; ++e) { const int64_t p = cidx[e]; if (p >= p0 && p < p1) ++st[(size_t)(p - p0) + 1]; }
-      int64_t distinct = 0;
-      for (int64_t p = 0; p < p1 - p0; ++p) { distinct += st[(size_t)p + 1] != 0; st[(size_t)p + 1] += st[(size_t)p]; }
-      ecount[(size_t)tix + 1] = st[(size_t)(p1 - p0)];
-      dcount[(size_t)tix + 1] = distinct;
-    };
-    run_threads(nth, count);
-    for (int t = 0; t < nth; ++t) { ecount[(size_t)t + 1] += ecount[(size_t)t]; dcount[(size_t)t + 1] += dcount[(size_t)t]; }
-    rpos.resize((size_t)dcount[(size_t)nth]);
-    rptr.resize((size_t)dcount[(size_t)nth] + 1);
-    auto place = [&](int tix) {
-      const int64_t p0 = P * tix / nth, p1 = P * (tix + 1) / nth, q0 = ecount[(size_t)tix];
-      std::vector<int64_t>& st = start[(size_t)tix];
-      int64_t d = dcount[(size_t)tix];
-      for (int64_t p = 0; p < p1 - p0; ++p)
-        if (st[(size_t)p + 1] != st[(size_t)p]) { rpos[(size_t)d] = p0 + p; rptr[(size_t)d] = q0 + st[(size_t)p]; ++d; }
-      for (int64_t e = 0; e < nnz; ++e) {                          // e ascending: ties stay in constraint order
-        const int64_t p = cidx[e];
-        if (p < p0 || p >= p1) continue;
-        const int64_t q = q0 + st[(size_t)(p - p0)]++;
-        rcon[(size_t)q] = con[e];
-        rval[(size_t)q] = cval[e];
-      }
-    };
-    run_threads(nth, place);
-    rptr[(size_t)dcount[(size_t)nth]] = nnz;
-  }
-  clk.mark("CSR by position");
-  std::vector<int64_t> vcptr(cptr, cptr + m + 1), vcidx(cidx, cidx + nnz);
-  std::vector<double> vcval(cval, cval + nnz);
-  int rc = 0;
-  if ((rc = dev_upload(&D.cptr, vcptr, D.mem))) return rc;
-  if ((rc = dev_upload(&D.cidx, vcidx, D.mem))) return rc;
-  if ((rc = dev_upload(&D.cval, vcval, D.mem))) return rc;
-  if ((rc = dev_upload(&D.cwval, w, D.mem))) return rc;
-  if ((rc = dev_upload(&D.rpos, rpos, D.mem))) return rc;
-  if ((rc = dev_upload(&D.rptr, rptr, D.mem))) return rc;
-  if ((rc = dev_upload(&D.rcon, rcon, D.mem))) return rc;
-  if ((rc = dev_upload(&D.rval, rval, D.mem))) return rc;
-  if ((rc = dev_upload(&D.a_r, ar, D.mem))) return rc;
-  if ((rc = dev_upload(&D.a_c, ac, D.mem))) return rc;
-  if ((rc = dev_upload(&D.s_rloc, rloc, D.mem))) return rc;
-  if ((rc = dev_upload(&D.s_cloc, cloc, D.mem))) return rc;
-  if ((rc = dev_upload(&D.dlist, dl, D.mem))) return rc;
-  if ((rc = dev_upload(&D.slist, sl, D.mem))) return rc;
-  if ((rc = dev_upload(&D.kidx, kidx, D.mem))) return rc;
-  clk.mark("uploads");
-  D.md = (int64_t)dl.size();
-  D.ns = (int64_t)sl.size();
-  if (D.ns) {
-    int64_t kmax = 1;
-    for (int64_t q = 0; q < D.ns; ++q) kmax = std::max(kmax, c->h_kptr[q + 1] - c->h_kptr[q]);
-    const int64_t sepsum = std::max<int64_t>(1, S.sepptr[S.nsn]);
-    const int64_t trsm_cap = std::max<int64_t>(1, (D.max_rhs * D.tmplen) / sepsum);
-    const int64_t want = std::min<int64_t>((int64_t)kidx.size(), ((int64_t)256 << 20) / std::max<int64_t>(1, S.n * 8));
-    D.vcols = std::min(trsm_cap, std::max(kmax, want));
-    if ((rc = dev_alloc(&D.vbuf, D.vcols * S.n, D.mem))) return rc;
-    if (D.md && (rc = dev_alloc(&D.hd, D.md * D.md, D.mem))) return rc;
-  }
-  // entries grouped by (clique, constraint): the sweeps of the Schur complement build their input panels from these
-  if (nnz < ((int64_t)1 << 31) && S.nsn * (m + 1) <= ((int64_t)1 << 28)) {
-    std::vector<int32_t> kptr((size_t)(S.nsn * (m + 1)) + 1, 0), koff(nnz);
-    std::vector<double> kval(nnz);
-    // (a slot belongs to one constraint: counting and filling run over the constraints on host threads)
-    const unsigned hwc = std::thread::hardware_concurrency();
-    const int nthc = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hwc ? hwc : 1), (int64_t)16, m, nnz / 65536 + 1}));
-    auto over_constraints = [&](auto body) {
-      run_threads(nthc, [&](int tix) { for (int64_t j = tix; j < m; j += nthc) body(j); });
-    };
-    over_constraints([&](int64_t j) {
-      for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) kptr[(size_t)ek[e] * (m + 1) + j + 1]++;
-    });
-    // exclusive scan over (clique, constraint); slot (k, m) of a clique doubles as the start of clique k + 1
-    {
-      int64_t run = 0;
-      for (int64_t k = 0; k < S.nsn; ++k) {
-        for (int64_t j = 0; j <= m; ++j) {
-          const size_t idx = (size_t)k * (m + 1) + j;
-          const int32_t cnt = (j < m) ? kptr[idx + 1] : 0;
-          kptr[idx] = (int32_t)run;
-          if (j < m) run += cnt;
-        }
-      }
-    }
-    D.kc_maxlist = 0;             // over the cliques that can be members of a family (nn <= 16, na <= 64)
-    for (int64_t k = 0; k < S.nsn; ++k)
-      if (S.nn(k) <= 16 && S.na(k) <= 64)
-        for (int64_t j = 0; j < m; ++j) {
-          const size_t q = (size_t)k * (m + 1) + j;
-          D.kc_maxlist = std::max<int64_t>(D.kc_maxlist, kptr[q + 1] - kptr[q]);
-        }
-    // most entries of a (family, constraint) pair: the parent's own + its children's (the entry-driven family sweep of
-    // front_famt.hip turns every entry into one term of a rank-T product)
-    D.fam_maxterms = 0;
-    D.fam_meanterms = 0.0;
-    {
-      int64_t sum = 0, pairs = 0;
-      for (int64_t k = 0; k < S.nsn; ++k)
-        if (k < (int64_t)c->fam.size() && c->fam[k] == 2)
-          for (int64_t j = 0; j < m; ++j) {
-            int64_t tot = kptr[(size_t)k * (m + 1) + j + 1] - kptr[(size_t)k * (m + 1) + j];
-            for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) {
-              const size_t q = (size_t)S.chidx[q2] * (m + 1) + j;
-              tot += kptr[q + 1] - kptr[q];
-            }
-            D.fam_maxterms = std::max(D.fam_maxterms, tot);
-            sum += tot;
-            ++pairs;
-          }
-      if (pairs) D.fam_meanterms = (double)sum / (double)pairs;
-    }
-    D.kc_maxlist_large = 0;       // over the childless fronts beyond the small classes (sparse-input sweep of large fronts)
-    for (int64_t k = 0; k < S.nsn; ++k)
-      if ((S.nn(k) > 16 || S.na(k) > 64) && S.nn(k) <= 64 && S.na(k) <= 128 && S.chptr[k + 1] == S.chptr[k])
-        for (int64_t j = 0; j < m; ++j) {
-          const size_t q = (size_t)k * (m + 1) + j;
-          D.kc_maxlist_large = std::max<int64_t>(D.kc_maxlist_large, kptr[q + 1] - kptr[q]);
-        }
-    // closed-form Gram blocks of the family children (front_leafgram.hip): per child its entries over all constraints
-    // in constraint order (row | column << 8 | constraint << 16, value halved on the diagonal) -- static, so the pair
-    // kernel reads them with one coalesced load -- and the record size of the per-step tables
-    D.lg_children = 0; D.lg_maxent = 0; D.lg_pairs = 0; D.lg_rows = 0; D.lg_rec = 0;
-    c->lg_slot_of.assign((size_t)S.nsn, -1);
-    std::vector<int32_t> lg_eptr(1, 0);
-    for (int64_t k = 0; k < S.nsn; ++k)
-      if (k < (int64_t)c->fam.size() && c->fam[k] == 1) {
-        const int64_t E = kptr[(size_t)k * (m + 1) + m] - kptr[(size_t)k * (m + 1)];
-        c->lg_slot_of[(size_t)k] = (int32_t)D.lg_children++;
-        D.lg_maxent = std::max(D.lg_maxent, E);
-        D.lg_pairs += E * (E + 1) / 2;
-        D.lg_rows += S.nf(k) * S.nn(k);
-        D.lg_rec = std::max<int>(D.lg_rec, (int)(S.nf(k) * S.nf(k) + S.nf(k) * S.nn(k)));
-        lg_eptr.push_back(lg_eptr.back() + (int32_t)E);
-      }
-    // ... and the same positions as (row | column << 16) of the clique's panel, for k_fam_sparse (its members have < 2^16 rows)
-    std::vector<int32_t> kij(nnz);
-    {
-      std::vector<int32_t> fill(kptr.begin(), kptr.end() - 1);
-      over_constraints([&](int64_t j) {
-        for (int64_t e = cptr[j]; e < cptr[j + 1]; ++e) {
-          const int64_t nf = S.nf(ek[e]);
-          const int32_t q = fill[(size_t)ek[e] * (m + 1) + j]++;
-          koff[q] = eoff[e];
-          kval[q] = cval[e];
-          kij[q] = (int32_t)((eoff[e] % nf) & 0xffff) | (int32_t)((eoff[e] / nf) << 16);
-        }
-      });
-    }
-    kptr.pop_back();
-    D.kc_sorted = true;           // (CCS columns with ascending rows give ascending panel positions per clique)
-    for (size_t q = 0; q + 1 < kptr.size() && D.kc_sorted; ++q)
-      for (int32_t e = kptr[q] + 1; e < kptr[q + 1]; ++e)
-        if (koff[(size_t)e] <= koff[(size_t)e - 1]) { D.kc_sorted = false; break; }
-    clk.mark("entry tables");
-    if (D.lg_children > 0 && m < 32768) {
-      std::vector<int32_t> epk((size_t)lg_eptr.back()), remap((size_t)m, -1);
-      std::vector<double> ewv((size_t)lg_eptr.back());
-      for (int64_t k = 0; k < S.nsn; ++k) {
-        const int32_t g = c->lg_slot_of[(size_t)k];
-        if (g < 0) continue;
-        int32_t o = lg_eptr[(size_t)g];
-        for (int64_t j = 0; j < m; ++j)
-          for (int32_t q = kptr[(size_t)k * (m + 1) + j]; q < kptr[(size_t)k * (m + 1) + j + 1]; ++q, ++o) {
-            const int32_t i = kij[q] & 0xffff, jc = kij[q] >> 16;
-            epk[(size_t)o] = i | (jc << 8) | ((int32_t)j << 16);
-            ewv[(size_t)o] = i == jc ? 0.5 * kval[q] : kval[q];
-          }
-      }
-      for (size_t q = 0; q < dl.size(); ++q) remap[(size_t)dl[q]] = (int32_t)q;
-      if ((rc = dev_upload(&D.lg_eptr, lg_eptr, D.mem))) return rc;
-      if ((rc = dev_upload(&D.lg_epk, epk, D.mem))) return rc;
-      if ((rc = dev_upload(&D.lg_ew, ewv, D.mem))) return rc;
-      if ((rc = dev_upload(&D.lg_remap, remap, D.mem))) return rc;
-      if ((rc = dev_alloc(&D.lg_tab, D.lg_children * D.lg_rec, D.mem))) return rc;
-    }
-    clk.mark("leaf Gram tables");
-    // Static term lists of the family parents (fused extend-add, front_famt.hip lf_add_family): every entry of constraint j inside
-    // family f -- the parent's own and its children's -- as (vector ids vx | vy << 16, scale), the mapping k_fam_terms does per
-    // launch from the entry lists (front_famt.hip, header): own entry v at (i, j): e_i, e_j, v (v / 2 on the diagonal); child
-    // entry at (separator row a, column j): q~_{c,j}, e_{rel_c[a]}, -v; child entry at (i, j) of its supernode block: q~_{c,i},
-    // q~_{c,j}, v (v / 2).  Only when every family parent hangs under a large front whose packed triangle fits LDS.
-    if (D.fam_maxterms > 0 && famt_terms_ok(D) && !c->fam.empty()) {
-      std::vector<int32_t> fno((size_t)S.nsn, -1);
-      c->fz_levels.assign((size_t)S.nlev, 0);
-      int64_t nfam = 0;
-      bool ok = true;
-      for (int64_t k = 0; k < S.nsn; ++k)
-        if (c->fam[(size_t)k] == 2) {
-          fno[(size_t)k] = (int32_t)nfam++;
-          const int64_t par = S.snpar[k];
-          if (par < 0 || (size_t)par >= c->large_mask.size() || !c->large_mask[(size_t)par] || S.nf(par) > LF_ALDS_MAXNF) ok = false;
-          else c->fz_levels[(size_t)S.level[(size_t)par]] = 1;
-        }
-      if (ok && nfam > 0 && nfam < ((int64_t)1 << 19) && nfam * (m + 1) < ((int64_t)1 << 31)) {
-        // sizes first (a (family, constraint) list holds the parent's entries and its children's), then the lists themselves,
-        // the families spread over host threads
-        std::vector<int32_t> fptr((size_t)(nfam * (m + 1)) + 1, 0);
-        std::vector<int64_t> fam_k((size_t)nfam);
-        int64_t run = 0;
-        for (int64_t k = 0; k < S.nsn; ++k) {
-          const int32_t f = fno[(size_t)k];
-          if (f < 0) continue;
-          fam_k[(size_t)f] = k;
-          for (int64_t j = 0; j < m; ++j) {
-            fptr[(size_t)f * (m + 1) + j] = (int32_t)run;
-            run += kptr[(size_t)k * (m + 1) + j + 1] - kptr[(size_t)k * (m + 1) + j];
-            for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) {
-              const size_t q = (size_t)S.chidx[q2] * (m + 1) + j;
-              run += kptr[q + 1] - kptr[q];
-            }
-          }
-          fptr[(size_t)f * (m + 1) + m] = (int32_t)run;
-        }
-        fptr[(size_t)(nfam * (m + 1))] = (int32_t)run;
-        std::vector<int32_t> fpk((size_t)run);
-        std::vector<double> fsv((size_t)run);
-        const int nthf = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hwc ? hwc : 1), (int64_t)16, nfam / 16 + 1}));
-        run_threads(nthf, [&](int tix) {
-          for (int64_t f = tix; f < nfam; f += nthf) {
-            const int64_t k = fam_k[(size_t)f];
-            for (int64_t j = 0; j < m; ++j) {
-              size_t o = (size_t)fptr[(size_t)f * (m + 1) + j];
-              for (int32_t q = kptr[(size_t)k * (m + 1) + j]; q < kptr[(size_t)k * (m + 1) + j + 1]; ++q, ++o) {
-                const int32_t i = kij[q] & 0xffff, jc = kij[q] >> 16;
-                fpk[o] = i | (jc << 16);
-                fsv[o] = i == jc ? 0.5 * kval[q] : kval[q];
-              }
-              int32_t colbase = 0;
-              for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) {
-                const int64_t cc = S.chidx[q2];
-                const int32_t nnc = (int32_t)S.nn(cc);
-                const int32_t* rel = &S.relidx[S.sepptr[cc]];
-                for (int32_t q = kptr[(size_t)cc * (m + 1) + j]; q < kptr[(size_t)cc * (m + 1) + j + 1]; ++q, ++o) {
-                  const int32_t i = kij[q] & 0xffff, jc = kij[q] >> 16;
-                  if (i >= nnc) { fpk[o] = (FAMT_CHILD + colbase + jc) | (rel[i - nnc] << 16); fsv[o] = -kval[q]; }
-                  else { fpk[o] = (FAMT_CHILD + colbase + i) | ((FAMT_CHILD + colbase + jc) << 16); fsv[o] = i == jc ? 0.5 * kval[q] : kval[q]; }
-                }
-                colbase += nnc;
-              }
-            }
-          }
-        });
-        if ((rc = dev_upload(&D.fz_no, fno, D.mem))) return rc;
-        if ((rc = dev_upload(&D.fz_ptr, fptr, D.mem))) return rc;
-        if ((rc = dev_upload(&D.fz_pk, fpk, D.mem))) return rc;
-        if ((rc = dev_upload(&D.fz_s, fsv, D.mem))) return rc;
-        if ((rc = dev_alloc(&D.fz_slot, nfam + 8, D.mem))) return rc;      // (+ the eight task counters of k_lf_assemble_fz)
-        HIPCHK(hipMemset(D.fz_slot, 0, sizeof(int32_t) * (nfam + 8)));
-        D.fz_nfam = nfam;
-        D.fz_ok = true;
-      }
-    }
-    clk.mark("family term lists");
-    if ((rc = dev_upload(&D.kc_ij, kij, D.mem))) return rc;
-    if ((rc = dev_upload(&D.kc_ptr, kptr, D.mem))) return rc;
-    if ((rc = dev_upload(&D.kc_off, koff, D.mem))) return rc;
-    if ((rc = dev_upload(&D.kc_val, kval, D.mem))) return rc;
-  }
-  clk.mark("table uploads");
+  if (T.has_fz_levels) c->fz_levels = std::move(T.fz_levels);
+  if (T.has_fam_terms) { D.fz_nfam = T.fz_nfam; D.fz_ok = true; }
   D.ustack_cols = std::max(D.max_rhs, m);
-  if ((rc = dev_alloc(&D.ustack, D.ustack_cols * S.blklen(), D.mem))) return rc;
-  // entries the sweeps never write (strict upper triangles of the NN blocks) must stay finite
-  HIPCHK(hipMemset(D.ustack, 0, sizeof(double) * D.ustack_cols * S.blklen()));
-  clk.mark("swept stack");
   D.m = m;
-  D.cnnz = nnz;
-  D.rnnz = (int64_t)rpos.size();
+  D.cnnz = cptr[m];
+  D.rnnz = (int64_t)T.rpos.size();
   return 0;
 }
 

@@ -358,8 +358,7 @@ int init_gather_plan(csp_ctx* c, const InitTables& T, SetupClock& clk) {
     constexpr int32_t PLAN_MARK = INT32_MIN;
     std::vector<int64_t> nmark(par.size(), 0);
     {
-      const unsigned hw = std::thread::hardware_concurrency();
-      const int nth = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(hw ? hw : 1), (int64_t)16, (int64_t)par.size() / 64 + 1}));
+      const int nth = host_threads(16, par.size() / 64 + 1);
       auto work = [&](int tix) {
         for (size_t x = (size_t)tix; x < par.size(); x += (size_t)nth) {
           const int64_t k = par[x];

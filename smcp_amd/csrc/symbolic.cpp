@@ -1,5 +1,6 @@
 // Host symbolic analysis. See symbolic.hpp for what it replaces in the reference.
 #include "symbolic.hpp"
+#include "hostpar.hpp"
 #include "switches.hpp"
 
 #include <algorithm>
@@ -538,7 +539,7 @@ static void index_map_range(const Symbolic& S, int64_t e0, int64_t e1, const int
 }
 void index_map(const Symbolic& S, int64_t cnt, const int64_t* I, const int64_t* J, int64_t* out) {
   const int64_t per = 1 << 17;
-  int nth = (int)std::min<int64_t>(std::min<int64_t>(8, std::max(1u, std::thread::hardware_concurrency())), (cnt + per - 1) / per);
+  const int nth = host_threads(8, (cnt + per - 1) / per);
   if (nth <= 1) { index_map_range(S, 0, cnt, I, J, out); return; }
   std::vector<std::thread> th;
   const int64_t chunk = (cnt + nth - 1) / nth;

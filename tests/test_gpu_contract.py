@@ -424,3 +424,44 @@ def test_growing_max_rhs_replaces_the_workspaces():
     assert grown.device_bytes() == direct.device_bytes() > b4
     grown.device_init(0, 4)
     assert grown.device_bytes() == direct.device_bytes()
+
+
+# ---- invalid constraint sets ----------------------------------------------------------------------------------------------
+def test_an_invalid_constraint_set_leaves_nothing_behind():
+    """kkt_set_constraints releases the outgoing set, then refuses a set with a position outside blkval or in the strict upper
+    triangle of an NN block.  A valid set installed afterwards gives the Schur complement (fixed-order kernels: bit for bit)
+    and the device bytes of a context that never saw the refused ones."""
+    pat = problems.band_pattern(40, 3)
+
+    def schur(with_invalid):
+        symb = Symbolic(pat)
+        symb.device_init(0, 4)
+        chordal.tune(symb, chordal.TUNE_DETERMINISTIC, 1)
+        A = problems.random_factor_blkval(symb, 7)
+        orc.llt(orc.Sym(symb), A)
+        L = to_dev(symb, A)
+        chordal.cholesky(L)
+        Y = L.copy()
+        chordal.projected_inverse(Y)
+        cptr, cidx, cval = problems.random_constraints(symb, 3, density=0.2, seed=4)
+        if with_invalid:
+            nn, na = symb.clique_sizes()
+            k = int(np.flatnonzero(nn >= 2)[0])
+            upper = int(symb.blkptr[k]) + int(nn[k] + na[k])           # (row 0, column 1) of the clique's panel
+            for where, pos in ((0, symb.blklen), (len(cidx) - 1, upper)):
+                bad = cidx.copy()
+                bad[where] = pos
+                with pytest.raises(RuntimeError, match="invalid argument"):
+                    KKTSystem(symb, cptr, bad, cval, max_rhs=4)
+        sysk = KKTSystem(symb, cptr, cidx, cval, max_rhs=4)
+        sysk.build_schur(L, Y)
+        torch.cuda.synchronize()
+        chordal.check_status(symb)
+        return sysk.H.cpu().numpy(), symb.device_bytes()
+
+    H1, b1 = schur(True)
+    H0, b0 = schur(False)
+    print("device bytes with and without the refused sets:", b1, b0)
+    assert np.isfinite(H0).all() and np.abs(H0).max() > 0
+    assert np.array_equal(H1, H0)
+    assert b1 == b0
