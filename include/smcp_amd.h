@@ -323,6 +323,28 @@ int kkt_qr_solve(csp_ctx* ctx, const double* L, const double* Y, double kk, doub
  * optional) <- Gram matrix of the current stack in the weighted inner product (Q^T Q; the identity after a
  * factorisation).  Synchronises the stream. */
 int kkt_qr_inspect(csp_ctx* ctx, double* Rt_host, double* G_dev, void* stream);
+/* kkt_qr_solve for a BLOCK of nrhs right-hand sides on one kkt_qr_factor (csrc/kkt_qr_many.hip): row r of BX is a blkval at
+ * BX + r * ldbx, row r of BY a vector of length m at BY + r * ldby; every pair is overwritten with the (x, y) kkt_qr_solve
+ * computes for it, with the same kk for all rows.  Q is read twice per chunk of rows instead of twice per row; every stage is
+ * one launch sequence for the rows of a chunk.  Entries of a row beyond blklen / m are never written; L, Y, Q and R are only
+ * read: THE Q FACTOR STAYS VALID and kkt_qr_solve keeps working afterwards.  A row's result does not depend on what the other
+ * rows hold.
+ * CHUNKS.  A chunk is min(max_rhs, 16) rows (kkt_qr_solve_many_chunk): what the Hessian sweeps take on this context, capped at
+ * the sixteen columns of one tile of the two products with Q.  A larger nrhs is processed in chunks of that size.
+ * WORKSPACE.  (ceil(blklen / p) + 2) * 16 * m doubles with p = 2048 * ceil(blklen / 2^22) -- at most (ceil(blklen / 2048) + 2) * 16 * m
+ * -- of its own in the context's ledger (csp_device_bytes), allocated at the first call and kept; the workspace of kkt_qr_factor, which holds R, is not touched.
+ * SMCP_EINVAL, nothing written: nrhs < 1; ldbx < blklen or ldby < m with nrhs > 1; no constraints installed; no valid Q, or Q
+ * factored for another (L, Y) (as kkt_qr_solve); BX and BY overlapping by address range; BX or BY overlapping the stack or a QR
+ * workspace; a context under a subtree partition over more than one rank.  The any-size route (CSP_TUNE_DETERMINISTIC /
+ * SMCP_GENERIC) is accepted, as by kkt_qr_solve (kkt_qr_factor refuses it): the Hessian sweeps then sum in a fixed order, as the
+ * kernels of this call always do, and the same call gives the same bits on every pattern -- on the default route only where the
+ * sweeps themselves do (no small front with several children).
+ * chol(Y_AA) is formed again when another factorisation has replaced it in the cache, as by kkt_qr_solve, which reads no
+ * verdict of it back; under csp_lazy_status a failure is latched for csp_status.  Does not synchronise. */
+int kkt_qr_solve_many(csp_ctx* ctx, const double* L, const double* Y, double kk, double* BX, int64_t ldbx, double* BY,
+                      int64_t ldby, int64_t nrhs, void* stream);
+/* The chunk rule of kkt_qr_solve_many: min(max_rhs, 16), 0 when max_rhs < 1.  Host only: needs neither a context nor a device. */
+int64_t kkt_qr_solve_many_chunk(int64_t max_rhs);
 
 /* ---- subtree-sharded multi-GPU Schur complement (Gram formulation) ---------------------------
  * The elimination tree is cut into subtrees owned by single ranks plus a replicated top

@@ -92,6 +92,8 @@ SIGNATURES = {
     "kkt_qr_factor": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "kkt_qr_solve": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_vp, c_vp]),
     "kkt_qr_inspect": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "kkt_qr_solve_many": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
+    "kkt_qr_solve_many_chunk": (c_i64, [c_i64]),
 }
 
 _lib = None

@@ -76,6 +76,7 @@ enum {
   KID_trmm_n, KID_trmm_t, KID_trmm_mm, KID_trmm_combine, KID_syr2k_fma, KID_syr2k_mm,
   KID_symm_fma, KID_symm_mm, KID_symm_combine,
   KID_potrs_many_small, KID_potrs_many_step, KID_aadj_sub_many, KID_kkt_many_y, KID_kkt_many_scale,
+  KID_qr_dots_many, KID_qr_many_sum, KID_qr_many_small, KID_qr_many_mid, KID_qr_comb_many,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -99,7 +100,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_psd_zero", "k_psd_scatter", "k_psd_solve", "k_psd_fill", "k_top_chol", "k_lf_trtri",
   "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm",
   "k_symm_fma", "k_symm_mm", "k_symm_combine",
-  "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale"};
+  "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale",
+  "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2816,3 +2818,4 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 #include "kkt.hip"
 #include "kkt_many.hip"
 #include "kkt_qr.hip"
+#include "kkt_qr_many.hip"

@@ -139,10 +139,13 @@ struct ConstraintBufs {
   double* qr_ws = nullptr;
   int64_t qr_len = 0;
   bool qr_valid = false;       // ustack holds Q and qr_ws the factor for the matrices (qr_L, qr_Y)
+  // kkt_qr_solve_many (csrc/kkt_qr_many.hip): partial sums of Q^T r, x and the forward solution of a chunk (grown by dev_grow)
+  double* qrm_ws = nullptr;
+  int64_t qrm_len = 0;
   void release(DevLedger& mem) {
     dev_free(mem, cptr, cidx, cval, cwval, rpos, rptr, rcon, rval, ustack, a_r, a_c, s_rloc, s_cloc, dlist, slist, kidx);
     dev_free(mem, kc_ptr, kc_off, kc_val, kc_ij, fz_no, fz_slot, fz_ptr, fz_pk, fz_s, vbuf, hd);
-    dev_free(mem, lg_eptr, lg_epk, lg_ew, lg_remap, lg_tab, scm_owner, qr_ws, gpart, gsl_start, gsl_len, lg_list, lg_slot);
+    dev_free(mem, lg_eptr, lg_epk, lg_ew, lg_remap, lg_tab, scm_owner, qr_ws, qrm_ws, gpart, gsl_start, gsl_len, lg_list, lg_slot);
     *this = ConstraintBufs();
   }
 };

@@ -228,6 +228,29 @@ bool ranges_overlap(const double* a, int64_t alen, const double* b, int64_t blen
   return a0 < b1 && b0 < a1;
 }
 
+// The two halves of the blocked solve beyond n = 128, ceil(n / 64) block steps each (potrs_many_impl runs one after the other;
+// kkt_qr_solve_many puts its update of the forward solution between them).  Yw: n x nrhs, leading dimension n.
+// forward: Yw <- L^-1 B (the rows of B below each solved block are updated in place)
+void potrs_many_fwd(csp_ctx* c, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, double* Yw, int mm, hipStream_t st) {
+  const unsigned ncb = (unsigned)((nrhs + PM_CB - 1) / PM_CB);
+  for (int jb = 0; jb < (int)n; jb += LB) {
+    const int w = (int)std::min<int64_t>(LB, n - jb);
+    const int rest = (int)n - jb - w;
+    launch(c, KID_potrs_many_step, k_potrs_many_step, dim3((unsigned)std::max(1, (rest + 63) / 64), ncb), dim3(256), st, A, (int)n, lda, jb, w, B, ldb,
+           Yw, n, (int)nrhs, 0, mm);
+  }
+}
+// backward: B <- L^-T Yw (the rows of Yw above each solved block are updated in place)
+void potrs_many_bwd(csp_ctx* c, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, double* Yw, int mm, hipStream_t st) {
+  const unsigned ncb = (unsigned)((nrhs + PM_CB - 1) / PM_CB);
+  const int64_t nblocks = (n + LB - 1) / LB;
+  for (int jb = (int)((nblocks - 1) * LB); jb >= 0; jb -= LB) {
+    const int w = (int)std::min<int64_t>(LB, n - jb);
+    launch(c, KID_potrs_many_step, k_potrs_many_step, dim3((unsigned)std::max(1, jb / 64), ncb), dim3(256), st, A, (int)n, lda, jb, w, Yw, n,
+           B, ldb, (int)nrhs, 1, mm);
+  }
+}
+
 // L L^T Z = B for a block: n <= 128 one launch, beyond 2 ceil(n / 64) block steps over the chip -- whatever nrhs is.
 int potrs_many_impl(csp_ctx* c, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, hipStream_t st) {
   DeviceCtx& D = c->D;
@@ -245,19 +268,8 @@ int potrs_many_impl(csp_ctx* c, const double* A, int64_t n, int64_t lda, double*
   // the updates of the other rows: FMA below eight columns of a workgroup's block, tile products on the matrix cores from eight on
   // (the gate of csp_trmm / csp_symm); SMCP_POTRS_MANY_MM=0: FMA only.  Read on every call: tools/solve_many_time.py alternates the two
   const int mm = (sw_int("SMCP_POTRS_MANY_MM", 1) && !use_generic(c)) ? 1 : 0;
-  const unsigned ncb = (unsigned)((nrhs + PM_CB - 1) / PM_CB);
-  const int64_t nblocks = (n + LB - 1) / LB;
-  for (int jb = 0; jb < (int)n; jb += LB) {
-    const int w = (int)std::min<int64_t>(LB, n - jb);
-    const int rest = (int)n - jb - w;
-    launch(c, KID_potrs_many_step, k_potrs_many_step, dim3((unsigned)std::max(1, (rest + 63) / 64), ncb), dim3(256), st, A, (int)n, lda, jb, w, B, ldb,
-           Yw, n, (int)nrhs, 0, mm);
-  }
-  for (int jb = (int)((nblocks - 1) * LB); jb >= 0; jb -= LB) {
-    const int w = (int)std::min<int64_t>(LB, n - jb);
-    launch(c, KID_potrs_many_step, k_potrs_many_step, dim3((unsigned)std::max(1, jb / 64), ncb), dim3(256), st, A, (int)n, lda, jb, w, Yw, n,
-           B, ldb, (int)nrhs, 1, mm);
-  }
+  potrs_many_fwd(c, A, n, lda, B, nrhs, ldb, Yw, mm, st);
+  potrs_many_bwd(c, A, n, lda, B, nrhs, ldb, Yw, mm, st);
   return 0;
 }
 

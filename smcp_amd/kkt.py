@@ -37,6 +37,18 @@ def solve_many_chunks(nrhs, m, blklen, max_rhs):
     return [c] * (nrhs // c) + ([nrhs % c] if nrhs % c else [])
 
 
+def solve_many_qr_chunks(nrhs, max_rhs):
+    """The chunks KKTSystem.solve_many_qr processes nrhs right-hand sides in: every chunk but the last is what the Hessian sweeps
+    take on a context of max_rhs rows, capped at the column tile of the two products with Q (the rule of kkt_qr_solve_many
+    itself: include/smcp_amd.h kkt_qr_solve_many_chunk; host only)."""
+    if nrhs < 1:
+        raise ValueError("nrhs must be at least 1")
+    c = int(_lib.lib().kkt_qr_solve_many_chunk(int(max_rhs)))
+    if c < 1:
+        raise ValueError("max_rhs must be at least 1")
+    return [c] * (nrhs // c) + ([nrhs % c] if nrhs % c else [])
+
+
 def column_range(m, rank, world):
     """Contiguous block of Schur-complement columns owned by `rank` (balanced to within one column)."""
     return (m * rank) // world, (m * (rank + 1)) // world
@@ -740,21 +752,26 @@ class KKTSystem(ShardedSchur):
 
         return solve_
 
-    def solve_many(self, L, Y, BX, BY, kk):
-        """The solve_ of kkt_chol (solvers.py:506-541) for a block of right-hand sides on ONE factorisation: valid after
-        factor(L, Y) of this system.  BX: float64 device tensor (k, >= blklen) with stride(1) == 1, row r a blkval (the
-        batched form chordal.hessian accepts); BY: (k, >= m).  Every pair of rows is overwritten with its (x, y), the same
-        kk for all; entries beyond blklen / m stay.  Any k works on the workspace the system has: rows are processed in
-        chunks (solve_many_chunks).  Returns (BX, BY).  Not sharded (include/smcp_amd.h: kkt_solve_many)."""
-        if self._sharded_pair(L, Y):
-            raise NotImplementedError("solve_many has no sharded form: use the solve_ closure of factor(L, Y, group)")
-        bl, m = self.symb.blklen, self.m
-        for T, width, what in ((BX, bl, "BX"), (BY, m, "BY")):
+    def _check_block(self, BX, BY):
+        """the tensor contract of solve_many / solve_many_qr"""
+        for T, width, what in ((BX, self.symb.blklen, "BX"), (BY, self.m, "BY")):
             if not (torch.is_tensor(T) and T.dtype == torch.float64 and T.is_cuda and T.dim() == 2 and T.shape[0] >= 1
                     and T.shape[1] >= width and T.stride(1) == 1 and (T.shape[0] == 1 or T.stride(0) >= width)):
                 raise ValueError("%s must be a float64 device tensor (k, >= %d) with unit stride along a row" % (what, width))
         if BX.shape[0] != BY.shape[0]:
             raise ValueError("BX and BY must have the same number of rows")
+
+    def solve_many(self, L, Y, BX, BY, kk):
+        """The solve_ of kkt_chol (solvers.py:506-541) for a block of right-hand sides on ONE factorisation: valid after
+        factor(L, Y) of this system.  BX: float64 device tensor (k, >= blklen) with stride(1) == 1, row r a blkval (the
+        batched form chordal.hessian accepts); BY: (k, >= m).  Every pair of rows is overwritten with its (x, y), the same
+        kk for all; entries beyond blklen / m stay.  Any k works on the workspace the system has: rows are processed in
+        chunks (solve_many_chunks).  Returns (BX, BY).  Not sharded (include/smcp_amd.h: kkt_solve_many).
+        This is the block form of factor(); it rewrites the constraint stack, so the Q factor of a factor_qr is gone
+        afterwards.  The block form of factor_qr() is solve_many_qr."""
+        if self._sharded_pair(L, Y):
+            raise NotImplementedError("solve_many has no sharded form: use the solve_ closure of factor(L, Y, group)")
+        self._check_block(BX, BY)
         self._own()
         sync_cache(self.symb, L, Y)
         _chk(_lib.lib().kkt_solve_many(self.symb.handle, L.blkval.data_ptr(), Y.blkval.data_ptr(), self.H.data_ptr(), self.m,
@@ -777,7 +794,7 @@ class KKTSystem(ShardedSchur):
         _chk(_lib.lib().kkt_qr_factor(self.symb.handle, L.blkval.data_ptr(), Y.blkval.data_ptr(), ctypes.addressof(passes),
                                       ctypes.addressof(shift), _stream()), "kkt_qr_factor")
         self.qr_passes, self.qr_shift = passes.value, shift.value
-        epoch = self.symb.__dict__["_kkt_epoch"]
+        epoch = self._qr_epoch = self.symb.__dict__["_kkt_epoch"]
 
         def solve_(bx, by, kk):
             """Overwrites bx (cspmatrix) with x and by (device vector) with y."""
@@ -791,6 +808,26 @@ class KKTSystem(ShardedSchur):
             return bx, by
 
         return solve_
+
+    def solve_many_qr(self, L, Y, BX, BY, kk):
+        """The solve_ of kkt_qr (solvers.py:430-471) for a block of right-hand sides on ONE factorisation: valid after
+        factor_qr(L, Y) of this system, for as long as its closure is (a factor(), solve_many() or another KKTSystem on the
+        same Symbolic ends it).  BX, BY, kk and the result as in solve_many: every pair of rows is overwritten with its
+        (x, y), entries beyond blklen / m stay, rows go in chunks (solve_many_qr_chunks).  Q is read twice per chunk instead
+        of twice per right-hand side, and stays valid: the closure of factor_qr keeps working.  Returns (BX, BY).
+        This is the block form of factor_qr(); the block form of factor() is solve_many.  One GPU.  Bits repeat from call to
+        call wherever the Hessian sweeps' do -- always under chordal.tune(symb, TUNE_DETERMINISTIC, 1), which this call
+        accepts as the closure does (include/smcp_amd.h: kkt_qr_solve_many)."""
+        self._check_block(BX, BY)
+        if "_qr_epoch" not in self.__dict__:
+            raise RuntimeError("solve_many_qr needs the factor_qr(L, Y) of this system first")
+        if self.symb.__dict__.get("_kkt_epoch") != self._qr_epoch:
+            raise RuntimeError("the Q factor of this kkt_qr factorisation is gone: another KKTSystem has used "
+                               "the same Symbolic since factor_qr; factor again")
+        sync_cache(self.symb, L, Y)
+        _chk(_lib.lib().kkt_qr_solve_many(self.symb.handle, L.blkval.data_ptr(), Y.blkval.data_ptr(), float(kk), BX.data_ptr(),
+                                          BX.stride(0), BY.data_ptr(), BY.stride(0), BX.shape[0], _stream()), "kkt_qr_solve_many")
+        return BX, BY
 
     def qr_inspect(self):
         """(R^T as a host array, Q^T Q as a device tensor) of the last factor_qr -- test hook."""
