@@ -303,6 +303,38 @@ int64_t kkt_solve_many_chunk(int64_t m, int64_t blklen, int64_t max_rhs);
  * columns; the order of every sum is fixed.  SMCP_EINVAL: n < 1, lda < n, nrhs < 1, ldb < n with nrhs > 1, B overlapping
  * A.  Does not synchronise.  What kkt_solve_many calls; dense_potrs keeps its own routes. */
 int dense_potrs_many(csp_ctx* ctx, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, void* stream);
+/* kkt_res (solvers.py:401-411) for a BLOCK of nrhs iterates, with the norms of the DEBUG check of solve_ (534-538)
+ * (csrc/kkt_res_many.hip).  Rows as in kkt_solve_many: row r of XS / BX / RX is a blkval, row r of YS / BY / RY a vector of length m:
+ *   RX_r = -kk * W^-1(XS_r) + Aadj(YS_r) - BX_r      (W^-1 = csp_hessian(L, Y, ., adj = 2, inv = 1))
+ *   RY_r = Amap(XS_r) - BY_r
+ * norms: device pointer to 4 * nrhs doubles, or null.  norms[4 r + 0 .. 3] = ||RX_r||, ||RY_r||, ||BX_r||, ||BY_r||: the blkval
+ * norms are sqrt(dot(., .)) in the trace inner product of csp_dot (weight 1 on the diagonal of a supernode's diagonal block, 2 below
+ * it, the slots above it are not summed), the vector norms are Euclidean.  They stay on the device: the call does not wait for them.
+ * XS, YS, BX, BY, L and Y are only read; entries of a row of RX / RY beyond blklen / m are never written; a row's results are a
+ * function of that row alone.  What RX holds in the slots above the diagonal of a diagonal block is not specified.
+ * Needs the constraints and nothing else: no Schur complement, no Q; the constraint stack is not written, so the call is valid
+ * after kkt_schur_factor, after kkt_qr_factor (whose Q stays valid) or after neither.
+ * chol(Y_AA) and the inverse-form factors are prepared as csp_hessian(inv = 1) prepares them and the status of that preparation is
+ * returned as csp_hessian returns it (latched under csp_lazy_status); when they are cached for Y -- after any factor or solve on the
+ * pair -- nothing is read back and the call does not synchronise.  The inverse Hessian goes in chunks of max_rhs rows; the number
+ * of launches of a chunk does not depend on the rows in it.
+ * WORKSPACE, in the context's ledger (csp_device_bytes), released with the constraint set: blklen int32 (blkval position -> entry of
+ * Aadj, built at the first call after kkt_set_constraints; that call waits for the stream once) and min(max_rhs, 65535) * 1026
+ * doubles of partial sums.  Neither grows afterwards.
+ * Every sum has an order fixed by the shapes (a fixed partition of the positions, per-workgroup partial sums, one fixed-order
+ * final pass): the same RX gives the same norms bit for bit, and under CSP_TUNE_DETERMINISTIC the whole call repeats bit for bit.
+ * SMCP_EINVAL, nothing written: nrhs < 1; a leading dimension below blklen / m with nrhs > 1; no constraints installed; a null
+ * pointer among the eight blocks, L or Y; RX or RY overlapping, by address range, an input block, L, Y, each other or norms; norms
+ * overlapping an input; a context under a subtree partition over more than one rank. */
+int kkt_residual_many(csp_ctx* ctx, const double* L, const double* Y, double kk, const double* XS, int64_t ldxs,
+                      const double* YS, int64_t ldys, const double* BX, int64_t ldbx, const double* BY, int64_t ldby,
+                      double* RX, int64_t ldrx, double* RY, int64_t ldry, double* norms, int64_t nrhs, void* stream);
+/* The update of a refinement round for a block: XS_r <- XS_r - DX_r over the blkval, YS_r <- YS_r - DY_r over the m entries, one
+ * launch for all rows (65535 rows per launch).  Entries of a row beyond blklen / m are neither read nor written.  SMCP_EINVAL:
+ * nrhs < 1, a short leading dimension with nrhs > 1, no constraints installed (m is theirs), a null pointer, XS or YS overlapping
+ * another block.  Does not synchronise. */
+int kkt_update_many(csp_ctx* ctx, double* XS, int64_t ldxs, double* YS, int64_t ldys, const double* DX, int64_t lddx,
+                    const double* DY, int64_t lddy, int64_t nrhs, void* stream);
 
 /* kkt_qr(solvers.py:413-475 feas, 1843-1905 esd): the QR-based KKT solver.  kkt_qr_factor builds the stack of
  * half-Hessian images of ALL m constraints (call kkt_set_tnzcols(ctx, 0) before kkt_set_constraints: the reference

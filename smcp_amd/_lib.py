@@ -94,6 +94,9 @@ SIGNATURES = {
     "kkt_qr_inspect": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "kkt_qr_solve_many": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
     "kkt_qr_solve_many_chunk": (c_i64, [c_i64]),
+    "kkt_residual_many": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64,
+                                         c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kkt_update_many": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp]),
 }
 
 _lib = None

@@ -77,6 +77,7 @@ enum {
   KID_symm_fma, KID_symm_mm, KID_symm_combine,
   KID_potrs_many_small, KID_potrs_many_step, KID_aadj_sub_many, KID_kkt_many_y, KID_kkt_many_scale,
   KID_qr_dots_many, KID_qr_many_sum, KID_qr_many_small, KID_qr_many_mid, KID_qr_comb_many,
+  KID_res_inv_table, KID_res_combine, KID_res_y, KID_res_norms, KID_kkt_many_sub,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -101,7 +102,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_trmm_n", "k_trmm_t", "k_trmm_mm", "k_trmm_combine", "k_syr2k_fma", "k_syr2k_mm",
   "k_symm_fma", "k_symm_mm", "k_symm_combine",
   "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale",
-  "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many"};
+  "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many",
+  "k_res_inv_table", "k_res_combine", "k_res_y", "k_res_norms", "k_kkt_many_sub"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -1679,6 +1681,9 @@ void hess_up_fast(csp_ctx* c, double* U, int nrhs, int64_t ldu, const double* ys
     fprintf(stderr, "smcp_amd: level-0 cliques handed to a family launch that was never issued\n");
     if (!c->launch_err) c->launch_err = -1;
   }
+  // the fused extend-add belongs to THIS sweep: the extend-adds of other sweeps (the inverse Hessian of a residual straight after a
+  // Schur complement, a factorisation) must not find the flag of a sweep that is over
+  c->fz_live = false;
 }
 // the same for the cliques of a set of the partition (1 = owned, 2 = replicated top), root -> leaves
 void gather_set(csp_ctx* c, int set, const double* x, int64_t ldx, int nrhs, double* updbase, hipStream_t st) {
@@ -2817,5 +2822,6 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 
 #include "kkt.hip"
 #include "kkt_many.hip"
+#include "kkt_res_many.hip"
 #include "kkt_qr.hip"
 #include "kkt_qr_many.hip"

@@ -142,10 +142,17 @@ struct ConstraintBufs {
   // kkt_qr_solve_many (csrc/kkt_qr_many.hip): partial sums of Q^T r, x and the forward solution of a chunk (grown by dev_grow)
   double* qrm_ws = nullptr;
   int64_t qrm_len = 0;
+  // kkt_residual_many (csrc/kkt_res_many.hip): blkval position -> index into rpos (-1: no constraint entry there), built at the
+  // first call after kkt_set_constraints; the partial sums of the norms of a chunk of rows (both grown by dev_grow)
+  int32_t* rinv = nullptr;
+  int64_t rinv_len = 0;
+  double* res_ws = nullptr;
+  int64_t res_len = 0;
   void release(DevLedger& mem) {
     dev_free(mem, cptr, cidx, cval, cwval, rpos, rptr, rcon, rval, ustack, a_r, a_c, s_rloc, s_cloc, dlist, slist, kidx);
     dev_free(mem, kc_ptr, kc_off, kc_val, kc_ij, fz_no, fz_slot, fz_ptr, fz_pk, fz_s, vbuf, hd);
     dev_free(mem, lg_eptr, lg_epk, lg_ew, lg_remap, lg_tab, scm_owner, qr_ws, qrm_ws, gpart, gsl_start, gsl_len, lg_list, lg_slot);
+    dev_free(mem, rinv, res_ws);
     *this = ConstraintBufs();
   }
 };

@@ -829,6 +829,95 @@ class KKTSystem(ShardedSchur):
                                           BX.stride(0), BY.data_ptr(), BY.stride(0), BX.shape[0], _stream()), "kkt_qr_solve_many")
         return BX, BY
 
+    def residual_many(self, L, Y, XS, YS, BX, BY, kk, RX=None, RY=None, norms=None):
+        """kkt_res (solvers.py:401-411) for a block of iterates with the norms of the DEBUG check of solve_ (534-538): for every
+        row r
+            RX[r] = -kk * W^-1(XS[r]) + Aadj(YS[r]) - BX[r],   RY[r] = Amap(XS[r]) - BY[r],
+            norms[r] = ||RX[r]||, ||RY[r]||, ||BX[r]||, ||BY[r]||   (blkvals in the inner product of chordal.dot),
+        in one chain of launches per chunk of rows and without waiting for the device: the norms stay there.  XS, BX, RX: float64
+        device tensors (k, >= blklen) with stride(1) == 1, YS, BY, RY: (k, >= m), the contract of solve_many; norms: (k, 4),
+        contiguous.  Missing outputs are allocated.  The inputs, L and Y are only read, entries beyond blklen / m of the outputs
+        stay.  Needs no factorisation of this system and ends none: valid after factor(), after factor_qr() (whose closure and
+        solve_many_qr keep working) or after neither.  Returns (RX, RY, norms).  Not sharded (include/smcp_amd.h:
+        kkt_residual_many)."""
+        if self._sharded_pair(L, Y):
+            raise NotImplementedError("residual_many has no sharded form")
+        self._check_block(XS, YS)
+        self._check_block(BX, BY)
+        k = XS.shape[0]
+        if BX.shape[0] != k:
+            raise ValueError("XS and BX must have the same number of rows")
+        if RX is None:
+            RX = _empty(k * self.symb.blklen, self.dev).view(k, self.symb.blklen)
+        if RY is None:
+            RY = _empty(k * self.m, self.dev).view(k, self.m)
+        self._check_block(RX, RY)
+        if RX.shape[0] != k:
+            raise ValueError("XS and RX must have the same number of rows")
+        if norms is None:
+            norms = _empty(4 * k, self.dev).view(k, 4)
+        if not (torch.is_tensor(norms) and norms.dtype == torch.float64 and norms.is_cuda and norms.shape == (k, 4)
+                and norms.is_contiguous()):
+            raise ValueError("norms must be a contiguous float64 device tensor (%d, 4)" % k)
+        self._residual(L, Y, XS, YS, BX, BY, kk, RX, RY, norms.data_ptr(), k)
+        return RX, RY, norms
+
+    def _residual(self, L, Y, XS, YS, BX, BY, kk, RX, RY, norms_ptr, k):
+        self._own()
+        sync_cache(self.symb, L, Y)
+        _chk(_lib.lib().kkt_residual_many(self.symb.handle, L.blkval.data_ptr(), Y.blkval.data_ptr(), float(kk), XS.data_ptr(),
+                                          XS.stride(0), YS.data_ptr(), YS.stride(0), BX.data_ptr(), BX.stride(0), BY.data_ptr(),
+                                          BY.stride(0), RX.data_ptr(), RX.stride(0), RY.data_ptr(), RY.stride(0), norms_ptr, int(k),
+                                          _stream()), "kkt_residual_many")
+
+    def residual(self, L, Y, x, y, bx, by, kk):
+        """kkt_res (solvers.py:401-411) of one iterate: x, bx cspmatrix, y, by device vectors of length m; returns (r, rr) =
+        (-kk * W^-1(x) + Aadj(y) - bx, Amap(x) - by) as a new cspmatrix and a new vector.  The block entry with one row and no
+        norms."""
+        if self._sharded_pair(L, Y):
+            raise NotImplementedError("residual has no sharded form")
+        bl, m = self.symb.blklen, self.m
+        row = lambda t, n: t.view(1, n)
+        XS, YS, BX, BY = row(x.blkval, bl), row(y, m), row(bx.blkval, bl), row(by, m)
+        self._check_block(XS, YS)
+        self._check_block(BX, BY)
+        r = cspmatrix(self.symb, _empty(bl, self.dev))
+        r.touched()
+        rr = _empty(m, self.dev)
+        self._residual(L, Y, XS, YS, BX, BY, kk, row(r.blkval, bl), row(rr, m), None, 1)
+        return r, rr
+
+    def refine_many(self, L, Y, BX, BY, kk, rounds=1, qr=False, final=True):
+        """The solve_refined of the drivers (smcp_amd/solvers.py: solve, then `rounds` times residual -> solve -> subtract) for a
+        block of right-hand sides: B is kept, X <- solve(B), then R <- residual(X, B), D <- solve(R), X <- X - D.  The solve is
+        solve_many -- solve_many_qr with qr=True -- under the validity rules of those calls.  BX, BY (the contract of solve_many)
+        are overwritten with the refined (x, y), entries beyond blklen / m stay.  hist: device tensor (rounds + 1, k, 4), the
+        norms (residual_many) of the residual of the iterate before every round and of the final one; final=False skips the last
+        residual and returns `rounds` entries, the drivers' sequence with no extra sweep.  Nothing waits for the device or reads
+        a scalar back; the launches do not depend on k within a chunk.  Returns (BX, BY, hist)."""
+        rounds = int(rounds)
+        if rounds < 0:
+            raise ValueError("rounds must not be negative")
+        if self._sharded_pair(L, Y):
+            raise NotImplementedError("refine_many has no sharded form")
+        self._check_block(BX, BY)
+        solve = self.solve_many_qr if qr else self.solve_many
+        k, bl, m = BX.shape[0], self.symb.blklen, self.m
+        B0X, B0Y = BX[:, :bl].clone(), BY[:, :m].clone()
+        solve(L, Y, BX, BY, kk)
+        nres = rounds + (1 if final else 0)
+        hist = _empty(max(nres, 1) * k * 4, self.dev).view(max(nres, 1), k, 4)[:nres]
+        if nres:
+            RX, RY = _empty(k * bl, self.dev).view(k, bl), _empty(k * m, self.dev).view(k, m)
+        for j in range(rounds):
+            self.residual_many(L, Y, BX, BY, B0X, B0Y, kk, RX, RY, hist[j])
+            solve(L, Y, RX, RY, kk)
+            _chk(_lib.lib().kkt_update_many(self.symb.handle, BX.data_ptr(), BX.stride(0), BY.data_ptr(), BY.stride(0), RX.data_ptr(),
+                                            RX.stride(0), RY.data_ptr(), RY.stride(0), k, _stream()), "kkt_update_many")
+        if final:
+            self.residual_many(L, Y, BX, BY, B0X, B0Y, kk, RX, RY, hist[rounds])
+        return BX, BY, hist
+
     def qr_inspect(self):
         """(R^T as a host array, Q^T Q as a device tensor) of the last factor_qr -- test hook."""
         Rt = np.zeros((self.m, self.m), order="F")
