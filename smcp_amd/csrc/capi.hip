@@ -2019,6 +2019,8 @@ int hessian_impl(csp_ctx* c, const double* L, double* U, int64_t nrhs, int64_t l
 
 }  // namespace
 
+#include "dense_chol.hip"
+
 extern "C" {
 
 csp_ctx* csp_symbolic_create(int64_t n, const int64_t* colptr, const int64_t* rowind,
@@ -2099,13 +2101,12 @@ int csp_lazy_status(csp_ctx* c, int on) {
   c->lazy_status = on != 0;
   return 0;
 }
-static int flush_pending_potrf(csp_ctx* c, hipStream_t st, const void* only, bool drop);      // kkt.hip
 int csp_status(csp_ctx* c, void* stream) {
   if (int rc = ready(c)) return rc;
   hipStream_t st = (hipStream_t)stream;
   // a Schur complement that kkt_schur_factor left unfactored (deferred status) and nobody has used yet: its verdict belongs
   // to this read-out
-  if (int rc = flush_pending_potrf(c, st, nullptr, false)) return rc < 0 ? rc : rc;
+  if (int rc = chol_flush(c, st)) return rc;
   int v = 0;
   HIPCHK(hipMemcpyAsync(c->D.info_host + 16, c->D.info + 16, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));

@@ -165,6 +165,17 @@ struct RhsWorkspaces {
   void release(DevLedger& mem) { dev_free(mem, upd, updp, tmp); *this = RhsWorkspaces(); }
 };
 
+// Dense Cholesky of the Schur complement H.  To the context H is unknown, PENDING (built by kkt_schur_factor under deferred
+// status, waiting for its first reader) or FACTORED HERE (which selects the fast single-right-hand-side solves).  Only
+// dense_chol.hip reads or writes this; everyone else calls its chol_* functions.
+struct DenseChol {
+  // workspace of the blocked factorisation (n > 128), grown by dev_grow: nblocks * 4096 doubles, the inverses of the 64 x 64
+  // diagonal blocks (the operand of its panel kernels), then 2 n, the two work vectors of the step solve
+  double* ws = nullptr; int64_t cap = 0;
+  struct { const void* A = nullptr; int64_t n = 0; } factored;      // the latest factor made here, while nothing has overwritten ws
+  struct { double* H = nullptr; int64_t n = 0, ld = 0; hipStream_t stream = nullptr; } pending;
+};
+
 struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
   DevLedger mem;           // every device buffer this context holds (devmem.hpp)
   int device = -1;
@@ -214,11 +225,7 @@ struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
   int64_t fam_maxterms = 0;  // most entries of a (family, constraint) pair: the parent's own + its children's
   double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
   double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
-  // blocked dense Cholesky of the Schur complement: inverses of its 64 x 64 diagonal blocks (for the blocked potrs)
-  double* hinv = nullptr;    // nblocks * 4096 + 2 n doubles (the tail holds the two work vectors of the solve)
-  int64_t hinv_cap = 0, hinv_n = 0;
-  const void* hinv_tag = nullptr;   // the factor these inverses belong to
-  double* h_pending = nullptr; int64_t h_pending_n = 0, h_pending_ld = 0; hipStream_t h_pending_stream = nullptr;   // a Schur complement left unfactored by kkt_schur_factor (deferred status)
+  DenseChol chol;
   double* sw = nullptr;      // blklen : sqrt of the inner-product weights (Gram path)
   int lg_rec = 0;                                                     // doubles per child of the per-step tables (lg_tab)
   int lg_nf = 0, lg_nn = 0, lg_na = 0;                                // sizing over that list

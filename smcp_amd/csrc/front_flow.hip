@@ -8,7 +8,7 @@
 // flow_plan): only the owner ever reads or writes the tile in the matrix itself, so those accesses need no coherence
 // protocol at all.  What crosses workgroups is published once, write-through, in buffers nobody has read before:
 //   * P(i, j) -- the final panel tile L(i, j) -- as a packed 64 x 64 copy in a workspace, flag pflag[tile],
-//   * Dinv(j) -- the inverse of the diagonal block L(j, j) (what dense_potrs reads afterwards as well) --, flag dflag[j].
+//   * Dinv(j) -- the inverse of the diagonal block L(j, j) --, flag dflag[j].
 // (MI355X_MICROARCH.md, inter-workgroup visibility: payload stored sc1 by every lane, every storing wave drained, workgroup
 // barrier, ONE lane's sc1 flag store; the consumer polls the flag with ONE sc1 load per poll, a workgroup barrier, then
 // every load of the payload is an sc1 load, which bypasses the CU's L1 -- so two workgroups may share a CU.)

@@ -1,4 +1,4 @@
-// KKT layer on device: Amap / Aadj, Schur-complement build + factor, solve_ closure.
+// KKT layer on device: Amap / Aadj, Schur-complement build, solve_ closure (the dense Cholesky of H: dense_chol.hip).
 // Mirrors kkt_chol of src/python/solvers.py:477-541 (and Amap/Aadj 369-386); included by capi.hip.
 
 namespace {
@@ -128,271 +128,6 @@ __global__ void k_scm_columns(int64_t m, const int64_t* cptr, const int32_t* a_r
   if (lane == 0) { H[i + s * ldh] = acc; H[s + i * ldh] = acc; }
 }
 
-// single-workgroup dense Cholesky / triangular solves (generic path)
-__global__ void k_dense_potrf(double* A, int n, int64_t lda, int* info) {
-  int f = wg::potrf(n, A, lda);
-  if (f && threadIdx.x == 0) *info = f;
-}
-__global__ void k_dense_potrs(const double* A, int n, int64_t lda, double* B, int nrhs, int64_t ldb) {
-  wg::trsm_llN(n, nrhs, A, lda, B, ldb);
-  wg::trsm_llT(n, nrhs, A, lda, B, ldb);
-}
-// threads of the one-workgroup factorisation of H (SMCP_POTRF_THREADS, timing studies)
-static dim3 potrf_blk() {
-  static int t = 0;
-  if (!t) { const char* e = sw_str("SMCP_POTRF_THREADS"); t = e ? atoi(e) : 1024; if (t < 64 || t > 1024 || (t & 63)) t = 1024; }
-  return dim3(t);
-}
-// m <= 128: the whole factorisation in the LDS of one workgroup -- 16-wide block columns, diagonal blocks factored
-// and inverted by one wavefront (potrf_inv16), panel and trailing updates on MFMA (the scheme of k_factor_yaa_lds).
-// The inverses of the diagonal blocks are kept (dinv: 256 doubles per block) for k_dense_potrs_small.
-__global__ void __launch_bounds__(1024) k_dense_potrf_small(double* A, int n, int64_t lda, int* info, double* dinv) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int ld = n | 1;
-  double* const M = smem;
-  double* const D16 = smem + (int64_t)ld * n;
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e % n, j = e / n;
-    M[i + j * ld] = (i >= j) ? A[i + (int64_t)j * lda] : 0.0;
-  }
-  for (int jb = 0; jb < n; jb += 16) {
-    const int bw = min(16, n - jb);
-    const int f = potrf_inv16(M + jb + jb * ld, ld, bw, D16);
-    if (f) { if (threadIdx.x == 0) *info = jb + f; return; }
-    for (int e = threadIdx.x; e < 256; e += blockDim.x) dinv[(jb >> 4) * 256 + e] = D16[e];
-    const int mrem = n - jb - bw;
-    if (mrem > 0) {
-      double* Pj = M + (jb + bw) + jb * ld;
-      wg_mma(mrem, bw, bw, [=](int m, int kk) { return Pj[m + kk * ld]; },
-             [=](int kk, int nn_) { return D16[nn_ + kk * 16]; },
-             [=](int m, int nn_, double acc) { Pj[m + nn_ * ld] = acc; });
-      __syncthreads();
-      double* Tr = M + (jb + bw) + (jb + bw) * ld;
-      wg_mma(mrem, mrem, bw, [=](int m, int kk) { return Pj[m + kk * ld]; },
-             [=](int kk, int nn_) { return Pj[nn_ + kk * ld]; },
-             [=](int m, int nn_, double acc) { if (m >= nn_) Tr[m + nn_ * ld] -= acc; }, true);
-      __syncthreads();
-    }
-  }
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e % n, j = e / n;
-    if (i >= j) A[i + (int64_t)j * lda] = M[i + j * ld];
-  }
-}
-// Triangular solve with one 16 x 16 (bw x bw) diagonal block of the factor by ONE wavefront, by substitution
-// (backward stable; multiplying by the explicit block inverse costs the interior-point endgame several digits):
-// lane i holds entry i of the right-hand side and row i (trans 0: L y = t) or column i (trans 1: L^T x = t) of
-// the block in registers; the solved entries are broadcast with shuffles.  Returns entry `lane` of the solution.
-__device__ inline double wave_trsv16(const double* A, int64_t lda, int jb, int bw, double ti, int trans) {
-  const int i = threadIdx.x & 63;
-  double Lr[16];
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const bool in = i < bw && j < bw && (trans ? j >= i : j <= i);
-    Lr[j] = in ? (trans ? A[(jb + j) + (int64_t)(jb + i) * lda] : A[(jb + i) + (int64_t)(jb + j) * lda]) : (i == j ? 1.0 : 0.0);
-  }
-  double dii = 1.0;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) if (j == i) dii = Lr[j];
-  // one division per lane and call: a division inside each of the sixteen dependent steps was most of the chain
-  // (k_dense_potrs_small: 41 us at m = 100 whether the factor came from LDS or from global memory)
-  const double rdii = 1.0 / dii;
-  double xi = 0.0;
-  if (!trans) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const double xj = __shfl(ti * rdii, j, 64);
-      if (i == j) xi = xj;
-      if (i > j) ti -= Lr[j] * xj;
-    }
-  } else {
-#pragma unroll
-    for (int j = 15; j >= 0; --j) {
-      const double xj = __shfl(ti * rdii, j, 64);
-      if (i == j) xi = xj;
-      if (i < j) ti -= Lr[j] * xj;
-    }
-  }
-  return xi;
-}
-// A x = b with the factor of k_dense_potrf_small (one right-hand side, one workgroup, n <= 128).  The factor is copied to
-// LDS first (dynamic: n (n | 1) doubles): the 2 ceil(n / 16) block steps each read their diagonal block and the columns
-// below / beside it, and from global memory every step was two dependent round trips (41 us at m = 100, twice per solve_
-// of the interior-point iteration ... once per solve_); from LDS the steps are the substitution chains alone.
-__global__ void __launch_bounds__(256) k_dense_potrs_small(const double* Ag, int n, int64_t ldag, const double* dinv, double* b) {
-  extern __shared__ __attribute__((aligned(16))) double sAf[];
-  __shared__ double x[128], t[16];
-  const int tid = threadIdx.x;
-  const int lda = n | 1;
-  double* const A = sAf;
-  for (int e = tid; e < n * n; e += 256) {
-    const int i = e % n, j = e / n;
-    if (i >= j) A[i + j * lda] = Ag[i + (int64_t)j * ldag];
-  }
-  if (tid < n) x[tid] = b[tid];
-  __syncthreads();
-  for (int jb = 0; jb < n; jb += 16) {            // L y = b
-    const int bw = min(16, n - jb);
-    if (tid < 64) {
-      const double v = wave_trsv16(A, lda, jb, bw, tid < bw ? x[jb + tid] : 0.0, 0);
-      if (tid < bw) t[tid] = v;
-    }
-    __syncthreads();
-    if (tid < bw) x[jb + tid] = t[tid];
-    const int i = jb + bw + tid;
-    if (i < n) { double acc = 0.0; for (int j = 0; j < bw; ++j) acc += A[i + (int64_t)(jb + j) * lda] * t[j]; x[i] -= acc; }
-    __syncthreads();
-  }
-  for (int jb = ((n - 1) >> 4) << 4; jb >= 0; jb -= 16) {   // L^T x = y
-    const int bw = min(16, n - jb);
-    if (tid < 64) {
-      const double v = wave_trsv16(A, lda, jb, bw, tid < bw ? x[jb + tid] : 0.0, 1);
-      if (tid < bw) t[tid] = v;
-    }
-    __syncthreads();
-    if (tid < bw) x[jb + tid] = t[tid];
-    if (tid < jb) { double acc = 0.0; for (int j = 0; j < bw; ++j) acc += A[(jb + j) + (int64_t)tid * lda] * t[j]; x[tid] -= acc; }
-    __syncthreads();
-  }
-  if (tid < n) b[tid] = x[tid];
-}
-
-// One block step of the blocked triangular solves with the Cholesky factor A (lower, n x n).  Every workgroup
-// solves the 64-wide diagonal block redundantly (four 16-wide substitutions by wavefront 0, see wave_trsv16);
-// workgroup 0 publishes x_blk to xout; then the workgroups update their slice of the remaining rows:
-//   trans 0 (L y = b):    b[i] -= sum_j A[i, jb + j] x[j],  i >= jb + w   (one thread per row, coalesced)
-//   trans 1 (L^T x = y):  b[i] -= sum_j A[jb + j, i] x[j],  i <  jb       (one wave per row, lanes over j)
-__global__ void __launch_bounds__(256) k_dense_trsv_step(const double* A, int n, int64_t lda, const double* dinv, int jb, int w,
-                                                         double* b, double* xout, int trans) {
-  __shared__ double t[64], x[64];
-  const int tid = threadIdx.x;
-  if (tid < 64) t[tid] = tid < w ? b[jb + tid] : 0.0;
-  __syncthreads();
-  if (tid < 64) {
-    const int nsb = (w + 15) >> 4;
-    for (int q = 0; q < nsb; ++q) {
-      const int sb = trans ? nsb - 1 - q : q;          // forward: top sub-block first; transposed: bottom first
-      const int s0 = 16 * sb, bw = min(16, w - s0);
-      const double v = wave_trsv16(A, lda, jb + s0, bw, tid < bw ? t[s0 + tid] : 0.0, trans);
-      if (tid < bw) x[s0 + tid] = v;
-      // remaining sub-blocks of this diagonal block (same wavefront: LDS traffic is program-ordered)
-      if (!trans) {
-        const int i = s0 + bw + tid;
-        if (i < w) { double acc = 0.0; for (int j = 0; j < bw; ++j) acc += A[(jb + i) + (int64_t)(jb + s0 + j) * lda] * x[s0 + j]; t[i] -= acc; }
-      } else {
-        if (tid < s0) { double acc = 0.0; for (int j = 0; j < bw; ++j) acc += A[(jb + s0 + j) + (int64_t)(jb + tid) * lda] * x[s0 + j]; t[tid] -= acc; }
-      }
-    }
-    if (blockIdx.x == 0 && tid < w) xout[jb + tid] = x[tid];
-  }
-  __syncthreads();
-  if (!trans) {
-    const int i = jb + w + blockIdx.x * 256 + tid;
-    if (i < n) {
-      double acc = 0.0;
-      const double* Ai = A + i + (int64_t)jb * lda;
-      for (int j = 0; j < w; ++j) acc += Ai[(int64_t)j * lda] * x[j];
-      b[i] -= acc;
-    }
-  } else {
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int i = blockIdx.x * 4 + wave; i < jb; i += gridDim.x * 4) {
-      double acc = (lane < w) ? A[(jb + lane) + (int64_t)i * lda] * x[lane] : 0.0;
-      for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-      if (lane == 0) b[i] -= acc;
-    }
-  }
-}
-
-// A x = b with the Cholesky factor A (lower, n x n, 128 < n <= 1024), ONE right-hand side, in ONE launch of one workgroup:
-// the step kernel above is 2 ceil(n / 64) dependent launches of ~21 us (m = 1000, config 4: 32 launches, 0.76 ms per solve_ for
-// 8 MB of factor).  Here the chain is 2 ceil(n / 16) steps of one 16-wide substitution by wavefront 0 (wave_trsv16 on the
-// diagonal blocks, all of them staged in LDS up front: the same arithmetic, so the same backward-stable solve) followed by
-// the update of the other rows, one thread per row, whose sixteen factor entries were fetched a step ahead: the factor is
-// static, so its stream never waits for the chain.  x lives in LDS; barriers wait for LDS traffic only.
-// (Round 4 tried 64-wide steps through the diagonal blocks' cached inverses, x_blk = Dinv r_blk, the other rows updated in
-// four sub-steps of sixteen prefetched columns: 0.62 ms against 0.37 here -- a sub-step is 16 multiply-adds, far shorter
-// than the ~2.4 us a request to the 8 MB factor takes, and 128 registers per thread hold only one sub-step ahead, so the
-// kernel ran 256 exposed round trips where this one hides its 126 behind the one-wave substitutions.)
-constexpr int POTRS1_MAXN = 1024;
-__host__ __device__ inline size_t potrs_one_lds(int n) { return ((size_t)((n + 15) & ~15) * 17 + 16) * sizeof(double); }
-__global__ void __launch_bounds__(1024) k_dense_potrs_one(const double* A, int n, int64_t lda, double* b) {
-  extern __shared__ __attribute__((aligned(16))) double sm1[];
-  const int tid = threadIdx.x, npad = (n + 15) & ~15, nblk = npad >> 4;
-  double* const x = sm1;
-  double* const t = sm1 + npad;              // 16
-  double* const dg = t + 16;                 // nblk x 256: the diagonal 16 x 16 blocks (ld 16), identity beyond n
-  for (int e = tid; e < nblk * 256; e += 1024) {
-    const int blk = e >> 8, r = e & 15, cc = (e >> 4) & 15, i = 16 * blk + r, j = 16 * blk + cc;
-    dg[e] = (i < n && j < n && i >= j) ? A[i + (int64_t)j * lda] : (r == cc ? 1.0 : 0.0);
-  }
-  for (int e = tid; e < npad; e += 1024) x[e] = e < n ? b[e] : 0.0;
-  const int i = tid;                         // this thread's row (forward) / column (backward)
-  double va[16], vb[16];
-  // ---- L y = b
-  auto fetch_f = [&](int jb, double (&v)[16]) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = (i < n && i >= jb + 16 && jb + j < n) ? A[i + (int64_t)(jb + j) * lda] : 0.0;
-  };
-  auto step_f = [&](int blk, const double (&cur)[16]) {
-    const int jb = 16 * blk;
-    if (tid < 64) {
-      const double v = wave_trsv16(dg + 256 * blk, 16, 0, 16, tid < 16 ? x[jb + tid] : 0.0, 0);
-      if (tid < 16) t[tid] = v;
-    }
-    lds_barrier();
-    if (tid < 16) x[jb + tid] = t[tid];
-    if (i >= jb + 16 && i < n) {
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc += cur[j] * t[j];
-      x[i] -= acc;
-    }
-    lds_barrier();
-  };
-  fetch_f(0, va);
-  __syncthreads();
-  for (int blk = 0; blk < nblk; blk += 2) {
-    if (blk + 1 < nblk) fetch_f(16 * (blk + 1), vb);
-    step_f(blk, va);
-    if (blk + 1 < nblk) {
-      if (blk + 2 < nblk) fetch_f(16 * (blk + 2), va);
-      step_f(blk + 1, vb);
-    }
-  }
-  // ---- L^T x = y
-  auto fetch_b = [&](int jb, double (&v)[16]) {
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = (i < jb && jb + j < n) ? A[(jb + j) + (int64_t)i * lda] : 0.0;
-  };
-  auto step_b = [&](int blk, const double (&cur)[16]) {
-    const int jb = 16 * blk;
-    if (tid < 64) {
-      const double v = wave_trsv16(dg + 256 * blk, 16, 0, 16, tid < 16 ? x[jb + tid] : 0.0, 1);
-      if (tid < 16) t[tid] = v;
-    }
-    lds_barrier();
-    if (tid < 16) x[jb + tid] = t[tid];
-    if (i < jb) {
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc += cur[j] * t[j];
-      x[i] -= acc;
-    }
-    lds_barrier();
-  };
-  fetch_b(16 * (nblk - 1), va);
-  for (int blk = nblk - 1; blk >= 0; blk -= 2) {
-    if (blk >= 1) fetch_b(16 * (blk - 1), vb);
-    step_b(blk, va);
-    if (blk >= 1) {
-      if (blk >= 2) fetch_b(16 * (blk - 2), va);
-      step_b(blk - 1, vb);
-    }
-  }
-  if (tid < n) b[tid] = x[tid];
-}
-
 // y = a*y + x (length m), small
 __global__ void k_vec_axpby(int64_t m, double a, const double* x, double b, double* y) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -476,7 +211,7 @@ int kkt_set_constraints(csp_ctx* c, int64_t m, const int64_t* cptr, const int64_
   HIPCHK(hipSetDevice(D.device));
   // a Schur complement of the OUTGOING constraint set still waiting for its factorisation (deferred status): it is complete
   // and does not depend on what is replaced here -- factor it where it stands, on the stream it was built on
-  if (D.h_pending) { if (int rc = flush_pending_potrf(c, D.h_pending_stream, nullptr, false)) return rc; }
+  if (int rc = chol_flush_own_stream(c)) return rc;
   D.ConstraintBufs::release(D.mem);
   c->gsl_key.clear();
   SetupClock clk("kkt_set_constraints");
@@ -537,137 +272,6 @@ int kkt_aadj(csp_ctx* c, const double* y, double* X, void* stream) {
   if (int rc = ready(c)) return rc;
   if (!c->D.m) return SMCP_EINVAL;
   if (int rc = aadj_impl(c, y, X, (hipStream_t)stream)) return rc;
-  HIPCHK(end_call(c));
-  return 0;
-}
-
-// launches of the dense Cholesky of A (no status read-back); info: the failure flag the kernels set (the context's flag, or
-// a slot of its own when the factorisation runs on a side stream beside kernels that use the context's flag)
-static int potrf_launch(csp_ctx* c, double* A, int64_t n, int64_t lda, hipStream_t st, int* info) {
-  HIPCHK(hipMemsetAsync(info, 0, sizeof(int), st));
-  c->D.hinv_tag = nullptr;
-  static int oldp = -1;
-  if (oldp < 0) { const char* e = sw_str("SMCP_POTRF_OLD"); oldp = (e && e[0] == '1') ? 1 : 0; }
-  if (oldp || use_generic(c)) {
-    launch(c, KID_dense_potrf, k_dense_potrf, dim3(1), dim3(1024), st, A, (int)n, lda, info);
-    return 0;
-  }
-  if (n <= 2 * LB) {
-    const int64_t need = 8 * 256 + 2 * n;
-    if (int rc = dev_grow(&c->D.hinv, &c->D.hinv_cap, need, c->D.mem, st)) return rc;
-    const size_t lds = ((size_t)((n | 1) * n) + 256 + 8) * sizeof(double);
-    static bool attr_set = false;
-    if (!attr_set) {
-      HIPCHK(hipFuncSetAttribute((const void*)k_dense_potrf_small, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024));
-      attr_set = true;
-    }
-    launch_lds(c, KID_dense_potrf, k_dense_potrf_small, dim3(1), potrf_blk(), lds, st, A, (int)n, lda, info, c->D.hinv);
-    return 0;
-  }
-  // blocked right-looking Cholesky, 64-wide block columns: diagonal block by one workgroup, panel and
-  // trailing update as 64 x 64 MFMA tiles over the chip (the kernels of the large fronts, dense view)
-  MfmaArgs a = mfma_args(c, nullptr, 0, 1);
-  a.t.lev = c->D.lev3idx;
-  a.t.info = info;
-  a.lfd = c->D.lfd_dense;
-  a.dn = (int)n; a.dld = lda;
-  dim3 blk(256);
-  const int64_t nblocks = (n + LB - 1) / LB, need = nblocks * LB * LB + 2 * n;
-  if (int rc = dev_grow(&c->D.hinv, &c->D.hinv_cap, need, c->D.mem, st)) return rc;
-  // the whole blocked factorisation in ONE launch (front_flow.hip: tile dataflow inside the launch, the diagonal blocks' inverses
-  // straight to their slots); SMCP_FLOW=0 or beyond 4096: three launches per block column
-  if (flow_chol(c, st, A, lda, (int)n, c->D.hinv, nullptr, 5, info, 1)) return 0;
-  for (int jb = 0; jb < (int)n; jb += LB) {
-    a.lfd = c->D.hinv + (int64_t)(jb / LB) * LB * LB;      // the diagonal block's inverse goes straight to its slot (potrs reads it there)
-    launch_lds(c, KID_lf_diag, k_lf_diag, dim3(1), dim3(512), LF_DIAG_LDS, st, a, A, (double*)nullptr, 5, jb, 1);
-    const int mrem = (int)n - jb - LB;
-    if (mrem > 0) {
-      const int mt = tiles64(mrem);
-      launch(c, KID_lf_chol_panel, k_lf_chol_panel, dim3(mt, 1), blk, st, a, A, (double*)nullptr, 5, jb);
-      launch(c, KID_lf_chol_trail, k_lf_chol_trail, dim3(mt * (mt + 1) / 2, 1), blk, st, a, A, (double*)nullptr, 5, jb);
-    }
-  }
-  return 0;
-}
-// A Schur complement built by kkt_schur_factor under csp_lazy_status is left UNFACTORED until its first use: kkt_solve
-// then factors it on a side stream beside its first Hessian sweep (which does not read H), any other reader factors it
-// where it stands.  Drops the mark without factoring when the caller is about to factor or rebuild that matrix itself.
-static int flush_pending_potrf(csp_ctx* c, hipStream_t st, const void* only, bool drop) {
-  DeviceCtx& D = c->D;
-  if (!D.h_pending || (only && only != (const void*)D.h_pending)) return 0;
-  double* H = D.h_pending;
-  D.h_pending = nullptr;
-  if (drop) return 0;
-  if (int rc = potrf_launch(c, H, D.h_pending_n, D.h_pending_ld, st, c->D.info)) return rc;
-  HIPCHK(end_call(c));
-  int rc = fetch_info(c, st);
-  if (!rc && !use_generic(c)) { D.hinv_tag = H; D.hinv_n = D.h_pending_n; }
-  return rc;
-}
-int dense_potrf(csp_ctx* c, double* A, int64_t n, int64_t lda, void* stream) {
-  if (int rc = ready(c)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  flush_pending_potrf(c, st, A, true);
-  if (int rc = potrf_launch(c, A, n, lda, st, c->D.info)) return rc;
-  HIPCHK(end_call(c));
-  int rc = fetch_info(c, st);
-  if (!rc && !use_generic(c)) { c->D.hinv_tag = A; c->D.hinv_n = n; }
-  return rc;
-}
-// potrs with the factor of dense_potrf.  A single right-hand side of a factor produced by the blocked dense_potrf
-// (its diagonal-block inverses are still cached) runs as 2 * ceil(n / 64) block steps over the chip.
-static int potrs_impl(csp_ctx* c, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb, hipStream_t st) {
-  DeviceCtx& D = c->D;
-  static int olds = -1;
-  if (olds < 0) { const char* e = sw_str("SMCP_POTRS_OLD"); olds = (e && e[0] == '1') ? 1 : 0; }
-  if (olds) {
-    launch(c, KID_dense_potrs, k_dense_potrs, dim3(1), dim3(1024), st, A, (int)n, lda, B, (int)nrhs, ldb);
-    return 0;
-  }
-  if (nrhs == 1 && D.hinv_tag == A && D.hinv_n == n && n <= 2 * LB) {
-    static bool attr = false;
-    if (!attr) attr = hipFuncSetAttribute((const void*)k_dense_potrs_small, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) == hipSuccess;
-    launch_lds(c, KID_dense_potrs, k_dense_potrs_small, dim3(1), dim3(256), (size_t)n * (n | 1) * sizeof(double), st, A, (int)n, lda,
-               (const double*)D.hinv, B);
-    return 0;
-  }
-  static int steps_only = -1;
-  if (steps_only < 0) { const char* e = sw_str("SMCP_POTRS_STEPS"); steps_only = (e && e[0] == '1') ? 1 : 0; }
-  if (nrhs == 1 && n > 2 * LB && n <= POTRS1_MAXN && !steps_only && !use_generic(c)) {
-    // one launch of one workgroup: the whole substitution chain with the factor streamed a step ahead (k_dense_potrs_one)
-    static bool attr1 = false;
-    if (!attr1) attr1 = hipFuncSetAttribute((const void*)k_dense_potrs_one, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) == hipSuccess;
-    if (attr1 && potrs_one_lds((int)n) <= (size_t)(160 * 1024 - 1024)) {
-      launch_lds(c, KID_dense_potrs, k_dense_potrs_one, dim3(1), dim3(1024), potrs_one_lds((int)n), st, A, (int)n, lda, B);
-      return 0;
-    }
-  }
-  if (nrhs == 1 && D.hinv_tag == A && D.hinv_n == n && n > 2 * LB) {
-    const int64_t nblocks = (n + LB - 1) / LB;
-    double* y = D.hinv + nblocks * LB * LB;      // forward solution
-    double* z = y + n;                            // backward solution
-    for (int jb = 0; jb < (int)n; jb += LB) {
-      const int w = (int)std::min<int64_t>(LB, n - jb);
-      const int rest = (int)n - jb - w;
-      launch(c, KID_dense_potrs, k_dense_trsv_step, dim3((unsigned)std::max(1, (rest + 255) / 256)), dim3(256), st, A, (int)n, lda,
-             (const double*)(D.hinv + (int64_t)(jb / LB) * LB * LB), jb, w, B, y, 0);
-    }
-    for (int jb = (int)((nblocks - 1) * LB); jb >= 0; jb -= LB) {
-      const int w = (int)std::min<int64_t>(LB, n - jb);
-      launch(c, KID_dense_potrs, k_dense_trsv_step, dim3((unsigned)std::max(1, std::min(256, (jb + 3) / 4))), dim3(256), st, A, (int)n, lda,
-             (const double*)(D.hinv + (int64_t)(jb / LB) * LB * LB), jb, w, y, z, 1);
-    }
-    HIPCHK(hipMemcpyAsync(B, z, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    return 0;
-  }
-  launch(c, KID_dense_potrs, k_dense_potrs, dim3(1), dim3(1024), st, A, (int)n, lda, B, (int)nrhs, ldb);
-  return 0;
-}
-int dense_potrs(csp_ctx* c, const double* A, int64_t n, int64_t lda, double* B, int64_t nrhs, int64_t ldb,
-                void* stream) {
-  if (int rc = ready(c)) return rc;
-  if (int rc = flush_pending_potrf(c, (hipStream_t)stream, A, false)) return rc;
-  if (int rc = potrs_impl(c, A, n, lda, B, nrhs, ldb, (hipStream_t)stream)) return rc;
   HIPCHK(end_call(c));
   return 0;
 }
@@ -1143,7 +747,7 @@ int kkt_schur_columns(csp_ctx* c, const double* L, const double* Y, double* H, i
   if (!m || ldh < m || j0 < 0 || j1 > m || j0 > j1) return SMCP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   D.qr_valid = false;
-  flush_pending_potrf(c, st, H, true);
+  chol_drop_pending(c, H);
   HIPCHK(zero_flag(c, st));
   if (j0 == 0 && j1 == m && use_gram(c)) return schur_gram(c, L, Y, H, ldh, st);
   prepare_yaa(c, Y, false, st);
@@ -1172,7 +776,7 @@ int kkt_schur_gram_part(csp_ctx* c, const double* L, const double* Y, double* H,
   if (!D.m || ldh < D.m || nparts < 1 || part < 0 || part >= nparts || !use_gram(c)) return SMCP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   D.qr_valid = false;
-  flush_pending_potrf(c, st, H, true);
+  chol_drop_pending(c, H);
   HIPCHK(zero_flag(c, st));
   return schur_gram(c, L, Y, H, ldh, st, part, nparts);
 }
@@ -1192,23 +796,21 @@ static bool potrf_defer_on() {
 int kkt_schur_factor(csp_ctx* c, const double* L, const double* Y, double* H, int64_t ldh, void* stream) {
   // ONE matrix can wait for its factorisation: a pending Schur complement of another system on this context (two KKT systems
   // may share a Symbolic) is factored where it stands before this one takes the slot, so its solve_ never meets a raw H
-  if (c && c->D.h_pending && c->D.h_pending != H) { if (int rc = flush_pending_potrf(c, (hipStream_t)stream, nullptr, false)) return rc; }
+  if (c) { if (int rc = chol_flush(c, (hipStream_t)stream, nullptr, H)) return rc; }
   if (int rc = kkt_schur_columns(c, L, Y, H, ldh, 0, c ? c->D.m : 0, stream)) return rc;
   if (c->lazy_status && !use_generic(c) && potrf_defer_on() && Fork::enabled()) {
     // deferred status: nobody waits for potrf's verdict here, so the factorisation itself can wait for the first solve_
-    // (kkt_solve runs it beside its first Hessian sweep) or for whoever reads H first (flush_pending_potrf)
-    c->D.h_pending = H; c->D.h_pending_n = c->D.m; c->D.h_pending_ld = ldh; c->D.h_pending_stream = (hipStream_t)stream;
-    c->D.hinv_tag = nullptr;
+    // (kkt_solve runs it beside its first Hessian sweep) or for whoever reads H first (chol_flush)
+    chol_defer(c, H, c->D.m, ldh, (hipStream_t)stream);
     return 0;
   }
   return dense_potrf(c, H, c->D.m, ldh, stream);
 }
 // The caller is about to free (or reuse) the memory of H: whatever the context still remembers about it -- the mark of a
-// factorisation that kkt_schur_factor deferred, the cached inverses of its diagonal blocks -- is dropped, nothing is launched.
+// factorisation that kkt_schur_factor deferred, the mark of a factor made here -- is dropped, nothing is launched.
 int kkt_schur_forget(csp_ctx* c, const double* H) {
   if (!c || !H) return SMCP_EINVAL;
-  if ((const void*)c->D.h_pending == (const void*)H) c->D.h_pending = nullptr;
-  if (c->D.hinv_tag == (const void*)H) c->D.hinv_tag = nullptr;
+  chol_forget(c, H);
   return 0;
 }
 
@@ -1230,9 +832,7 @@ int kkt_solve(csp_ctx* c, const double* L, const double* Y, const double* H, int
   // a Schur complement that kkt_schur_factor left unfactored (deferred status): its Cholesky on a side stream beside the first
   // Hessian sweep, which does not read H -- with a failure flag of its own, latched by the branch itself
   std::unique_ptr<Fork> hf;
-  if (D.h_pending && (const void*)D.h_pending == (const void*)H) {
-    double* Hw = D.h_pending;
-    D.h_pending = nullptr;
+  if (double* Hw = chol_take_pending(c, H)) {
     // (only under deferred status: an eager caller -- the status regime may have been switched since kkt_schur_factor -- gets
     // the verdict of this factorisation as the return value, through the in-stream branch)
     hf.reset(c->lazy_status ? new Fork(c, st, 0) : nullptr);
@@ -1246,8 +846,8 @@ int kkt_solve(csp_ctx* c, const double* L, const double* Y, const double* H, int
       if (int rc = fetch_info(c, st)) return rc;
       HIPCHK(zero_flag(c, st));
     }
-    if (!use_generic(c)) { D.hinv_tag = H; D.hinv_n = m; }
-  } else if (int rc = flush_pending_potrf(c, st, nullptr, false)) return rc;    // (another matrix is pending: factor it where it stands)
+    chol_mark_factored(c, H, m);
+  } else if (int rc = chol_flush(c, st)) return rc;    // (another matrix is pending: factor it where it stands)
   // the Y_AA cache must correspond to (L, Y): recompute (cheap, one gather sweep)
   if (!(c->D.yaa_tag == Y && c->D.yaa_tag)) prepare_yaa(c, Y, false, st);
   if (!use_generic(c)) { if (int rc = prep_lk_cached(c, L, Y, st)) return rc; }

@@ -1,4 +1,5 @@
-// The kkt_qr solve for a block of right-hand sides: kkt_qr_solve_many; included by capi.hip after kkt_qr.hip and kkt_many.hip.
+// The kkt_qr solve for a block of right-hand sides: kkt_qr_solve_many; included by capi.hip after kkt_qr.hip; the triangular block
+// solves are dense_chol.hip's.
 // Row r of the block is the system of kkt_qr_solve, statement for statement (src/python/solvers.py:444-465), in the device's
 // normalisation (weights 1 on the diagonal and 2 below it, R stored as the lower Lc = R^T, no 0.5 factor):
 //   r1 = G(bx) -> xm = Q^T r1 (weighted) -> t = Lc^-1 by -> x = xm + kk t -> y = Lc^-T x -> bx = G^adj(Q x - r1) / kk.
@@ -263,7 +264,7 @@ int kkt_qr_solve_many(csp_ctx* c, const double* L, const double* Y, double kk, d
   HIPCHK(zero_flag(c, st));
   prepare_yaa(c, Y, true, st);
   if (int rc = prep_lk_cached(c, L, Y, st)) return rc;
-  const int mm = (sw_int("SMCP_POTRS_MANY_MM", 1) && !use_generic(c)) ? 1 : 0;      // (the gate of potrs_many_impl)
+  const int mm = potrs_many_mm(c);
   for (int64_t r0 = 0; r0 < nrhs; r0 += cmax) {
     const int k = (int)std::min(cmax, nrhs - r0);
     double* const bx = BX + r0 * ldbx;
@@ -275,8 +276,8 @@ int kkt_qr_solve_many(csp_ctx* c, const double* L, const double* Y, double kk, d
     if (m <= 2 * LB) {
       static bool attr = false;
       if (!attr) attr = hipFuncSetAttribute((const void*)k_qr_many_small, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024) == hipSuccess;
-      const size_t lds = ((size_t)m * (m | 1) + (size_t)PM_CBS * m) * sizeof(double);
-      launch_lds(c, KID_qr_many_small, k_qr_many_small, dim3((unsigned)((k + PM_CBS - 1) / PM_CBS)), dim3(256), lds, st, Lc, (int)m, m, XM, kk, by, k, ldby);
+      launch_lds(c, KID_qr_many_small, k_qr_many_small, dim3((unsigned)((k + PM_CBS - 1) / PM_CBS)), dim3(256), potrs_many_small_lds(m), st, Lc, (int)m, m, XM,
+                 kk, by, k, ldby);
     } else {
       potrs_many_fwd(c, Lc, m, m, by, k, ldby, T, mm, st);                                   // T = R^-T by                (452)
       launch(c, KID_qr_many_mid, k_qr_many_mid, dim3((unsigned)((m * k + 255) / 256)), dim3(256), st, m * k, kk, T, XM);   // x          (453)

@@ -586,7 +586,6 @@ void csp_symbolic_destroy(csp_ctx* c) {
   if (D.device >= 0) {
     hipSetDevice(D.device);
     if (c->side_fork) { Fork* f = (Fork*)c->side_fork; c->side_fork = nullptr; f->join(); delete f; }
-    D.h_pending = nullptr;      // (a deferred factorisation nobody asked for dies with the context)
     for (int q = 0; q < 2; ++q) {
       if (c->aux_stream[q]) { (void)hipStreamSynchronize(c->aux_stream[q]); (void)hipStreamDestroy(c->aux_stream[q]); }
       if (c->aux_join[q]) (void)hipEventDestroy(c->aux_join[q]);

@@ -62,11 +62,8 @@ static const Switch SWITCHES[] = {
   {"SMCP_ASM", "plan", "t: tiled extend-add kernel instead of the gather plan"},
   {"SMCP_ROOT_FUSED", "0", "1: fused two-product sweep of fronts without separator (Y_NN explicit: condition squared; studies only)"},
   {"SMCP_PD", "0", "1: four-wave tile products everywhere (no sixteen-wave shape for small launches)"},
-  {"SMCP_POTRF_OLD", "0", "1: generic one-workgroup dense Cholesky"},
   {"SMCP_FLOW", "1", "0: no one-launch blocked Cholesky with in-launch tile dataflow (front_flow.hip): per-step kernels for dense matrices / single fronts beyond 272 rows"},
   {"SMCP_FLOW_WG", "112", "workgroups of that launch (at most 112: four launches fit the chip side by side)"},
-  {"SMCP_POTRS_OLD", "0", "1: generic one-workgroup dense solve"},
-  {"SMCP_POTRS_STEPS", "0", "1: per-block launches of the dense solve instead of k_dense_potrs_one"},
   {"SMCP_POTRF_DEFER", "1", "0: kkt_schur_factor factors H at once even under deferred status"},
   {"SMCP_QR_TRSM", "mfma", "f: vector-FMA substitution kernel of kkt_qr instead of the MFMA one"},
   // ---- launch shapes and thresholds (timing studies)

@@ -424,6 +424,43 @@ def test_dense_potrf_potrs(n, pad):
         assert rel(np.tril(H2.cpu().numpy().T), Lref) < 1e-12
 
 
+@pytest.mark.parametrize("n", [5, 130, 1100])
+def test_dense_potrs_of_an_uploaded_factor(n):
+    """dense_potrs takes a Cholesky factor from anywhere: the fast single-right-hand-side routes below 129 and beyond 1024 are
+    for factors that dense_potrf made on this context (the step solve's work vectors are the tail of that factorisation's
+    workspace), every other factor takes a route that needs nothing from the context.  A fresh context on which no
+    factorisation has run, a factor from numpy with NaN above the diagonal and a leading dimension beyond the order; then a
+    factor made here, before and after kkt_schur_forget.  The sizes are the smallest on each side of the two route boundaries;
+    recipe and bound of test_dense_potrf_potrs."""
+    from smcp_amd import _lib
+    symb = Symbolic(GPU_PATTERNS["band"]())
+    chordal._ensure(symb)
+    lib = _lib.lib()
+    rng = np.random.default_rng(n)
+    M = rng.standard_normal((n, n))
+    Hh = M @ M.T + n * np.eye(n)
+    b = rng.standard_normal(n)
+    xref = np.linalg.solve(Hh, b)
+    ld = n + 3
+
+    def solve(A):
+        bd = torch.from_numpy(b.copy()).cuda()
+        assert lib.dense_potrs(symb.handle, A.data_ptr(), n, ld, bd.data_ptr(), 1, n, None) == 0
+        return bd.cpu().numpy()
+
+    Lp = np.zeros((n, ld))                               # (row r of this array = column r of the column-major matrix with ld rows)
+    Lp[:, :n] = np.linalg.cholesky(Hh).T
+    Lp[:, :n][np.tril_indices(n, -1)] = np.nan           # above the diagonal of the column-major factor
+    assert rel(solve(torch.from_numpy(Lp).cuda()), xref) < 1e-10
+    Hp = np.zeros((n, ld))
+    Hp[:, :n] = Hh
+    H = torch.from_numpy(Hp).cuda()
+    assert lib.dense_potrf(symb.handle, H.data_ptr(), n, ld, None) == 0
+    assert rel(solve(H), xref) < 1e-10
+    assert lib.kkt_schur_forget(symb.handle, H.data_ptr()) == 0
+    assert rel(solve(H), xref) < 1e-10
+
+
 @pytest.mark.parametrize("name,tnz", [("rand2", 0.3), ("arrow", 0.5), ("nested_mid", 0.2), ("diag", 0.5), ("arrow", 0.0)])
 def test_kkt_column_sparse_constraints(name, tnz):
     """Row a9: constraints touching few columns go through the SCMcolumn2 path (solvers.py:489-497,
