@@ -29,6 +29,8 @@
 #include "front_downfam.hip"
 #include "front_fam.hip"
 #include "front_upfam.hip"
+#include "front_cholfam.hip"
+#include "front_pinvfam.hip"
 #include "front_fam2.hip"
 #include "front_lfsp.hip"
 #include "front_leafgram.hip"
@@ -78,6 +80,7 @@ enum {
   KID_potrs_many_small, KID_potrs_many_step, KID_aadj_sub_many, KID_kkt_many_y, KID_kkt_many_scale,
   KID_qr_dots_many, KID_qr_many_sum, KID_qr_many_small, KID_qr_many_mid, KID_qr_comb_many,
   KID_res_inv_table, KID_res_combine, KID_res_y, KID_res_norms, KID_kkt_many_sub,
+  KID_chol_fam, KID_pinv_fam,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -103,7 +106,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_symm_fma", "k_symm_mm", "k_symm_combine",
   "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale",
   "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many",
-  "k_res_inv_table", "k_res_combine", "k_res_y", "k_res_norms", "k_kkt_many_sub"};
+  "k_res_inv_table", "k_res_combine", "k_res_y", "k_res_norms", "k_kkt_many_sub",
+  "k_chol_fam", "k_pinv_fam"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2178,6 +2182,114 @@ int csp_index_map(const csp_ctx* c, int64_t cnt, const int64_t* I, const int64_t
 
 #include "setup.hip"
 
+namespace {
+
+// ---- families at the scaling point (front_cholfam.hip, front_pinvfam.hip): the family parents of level 1 with their childless
+// children of level 0 in one launch each way; the level-0 cliques outside the families ride along when they fit (lone).
+// SMCP_SCALING_FAM=0: the per-level launches.  The plan is one per call and the same for both directions.
+struct ScalFam {
+  bool on = false;
+  MfmaArgs af;                      // the family parents: list af.t.lev, nfam of them
+  int nfam = 0;
+  const int32_t* lone = nullptr;    // level-0 cliques outside the families, when they ride along
+  int nlone = 0, lnn = 0, lna = 0;
+  int nfmax = 0, cpan = 0, sel = 0;
+  size_t bytes = 0;
+};
+ScalFam scaling_fam_plan(csp_ctx* c, const MfmaArgs& a0, int set) {
+  ScalFam p;
+  static const int on = sw_on("SMCP_SCALING_FAM", 1);
+  // (a set partition brings level sets of its own; replicated trial factorisations keep the per-level route)
+  if (!on || set || use_generic(c) || fam_off() || c->verify_cache || c->ntrial != 1 || c->sets[1].lev2 || c->sets[2].lev2 || c->S.nlev < 2) return p;
+  const LevelClass& L0 = c->lvl[0];
+  const LevelClass& L1 = c->lvl[1];
+  if (!L1.nI || !L1.nS || !L0.nS) return p;
+  for (int64_t l = 2; l < c->S.nlev; ++l) if (c->lvl[(size_t)l].nS) return p;      // (family parents sit at level 1: their children are leaves)
+  if (L1.famnn > 16 || L1.famna > 64 || L1.famcnn > 16 || L1.famcna > 32) return p;
+  p.af = a0;
+  p.af.t.lev = c->D.lev2idx + c->S.levptr[1] + (L1.nI - L1.nS);
+  p.af.level = 1;
+  p.af.famna = L1.famna; p.af.famnn = L1.famnn; p.af.famcna = L1.famcna; p.af.famcnn = L1.famcnn;
+  p.nfam = (int)L1.nS;
+  // the decision on the outsiders is one per class, on the maxima over ALL small cliques of level 0 (as in hess_up_fast)
+  const int nout = (int)(L0.nI - L0.nS);
+  if (nout > 0 && L0.nnmaxI <= 16 && L0.namaxI <= 64) { p.lone = c->D.lev2idx + c->S.levptr[0]; p.nlone = nout; p.lnn = L0.nnmaxI; p.lna = L0.namaxI; }
+  p.nfmax = std::max(L1.famnn + L1.famna, p.lnn + p.lna);
+  p.cpan = (L1.famcnn + L1.famcna) * L1.famcnn;
+  p.bytes = sfam_lds_bytes(p.nfmax, p.cpan);
+  if (p.bytes > 64 * 1024) return p;      // (the largest families take 59 KB: no size class needs the attribute for more)
+  const int pnat = (std::max(std::max((int)L1.famna, p.lna), 1) + 15) / 16, cnat = (std::max((int)L1.famcna, 1) + 15) / 16;
+  p.sel = 2 * pnat + cnat;
+  p.on = p.sel >= 3 && p.sel <= 10;
+  return p;
+}
+template <bool PREP>
+bool launch_chol_fam(csp_ctx* c, const ScalFam& p, double* x, double* lkout, hipStream_t st) {
+  const dim3 grid(p.nfam + p.nlone), blk(256);
+#define SMCP_CF(PN, CN) launch_lds(c, KID_chol_fam, k_chol_fam<PN, CN, PREP>, grid, blk, p.bytes, st, p.af, x, lkout, p.nfmax, p.cpan, p.nfam, p.lone); return true
+  switch (p.sel) {
+    case 3: SMCP_CF(1, 1);
+    case 4: SMCP_CF(1, 2);
+    case 5: SMCP_CF(2, 1);
+    case 6: SMCP_CF(2, 2);
+    case 7: SMCP_CF(3, 1);
+    case 8: SMCP_CF(3, 2);
+    case 9: SMCP_CF(4, 1);
+    case 10: SMCP_CF(4, 2);
+  }
+#undef SMCP_CF
+  return false;
+}
+// ap: the arguments of the root -> leaves pass (ap.t.upd: where the Y_AA blocks go, ap.LK: the inverse-form factor)
+bool launch_pinv_fam(csp_ctx* c, const ScalFam& p, const MfmaArgs& ap, double* x, hipStream_t st) {
+  MfmaArgs af = p.af;
+  af.t.upd = ap.t.upd; af.LK = ap.LK;
+  const dim3 grid(p.nfam + p.nlone), blk(256);
+#define SMCP_PF(PN, CN) launch_lds(c, KID_pinv_fam, k_pinv_fam<PN, CN>, grid, blk, p.bytes, st, af, x, p.nfmax, p.cpan, p.nfam, p.lone); return true
+  switch (p.sel) {
+    case 3: SMCP_PF(1, 1);
+    case 4: SMCP_PF(1, 2);
+    case 5: SMCP_PF(2, 1);
+    case 6: SMCP_PF(2, 2);
+    case 7: SMCP_PF(3, 1);
+    case 8: SMCP_PF(3, 2);
+    case 9: SMCP_PF(4, 1);
+    case 10: SMCP_PF(4, 2);
+  }
+#undef SMCP_PF
+  return false;
+}
+// the levels 0 and 1 of a leaves -> root / root -> leaves pass with the family launch in them: small(am, cnt) is the per-level
+// launch of a list of small cliques, large(am, cnt, l) that of a level's large fronts, fam() the family launch.
+// Leaves -> root: the family launch (with the lone cliques) is the first of level 1 -- a front of level 1 outside the families may
+// be the parent of a level-0 outsider; outsiders that do not ride along keep their launch at level 0.
+template <class Small, class Large, class Fam>
+void scaling_fam_up(csp_ctx* c, const ScalFam& p, const MfmaArgs& a0, Small small, Large large, Fam fam) {
+  for (int64_t l = 0; l < 2; ++l) {
+    if (l == 1) fam();
+    for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t, int thr) {
+      if (!lds) { large(am, cnt, l); return; }
+      cnt -= am.nS;
+      if (cnt > 0 && !(l == 0 && p.nlone)) small(am, cnt, thr);
+    });
+  }
+}
+// Root -> leaves: level 1 outside the families first, then the family launch at level 0's turn (a lone clique may hang off any
+// front above), then whatever of level 0 does not ride along
+template <class Small, class Large, class Fam>
+void scaling_fam_down(csp_ctx* c, const ScalFam& p, const MfmaArgs& a0, Small small, Large large, Fam fam) {
+  for (int64_t l = 1; l >= 0; --l) {
+    if (l == 0) fam();
+    for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t, int thr) {
+      if (!lds) { large(am, cnt, l); return; }
+      cnt -= am.nS;
+      if (cnt > 0 && !(l == 0 && p.nlone)) small(am, cnt, thr);
+    });
+  }
+}
+
+}  // namespace
+
 extern "C" {
 
 int64_t csp_device_bytes(const csp_ctx* c) { return c ? c->D.mem.total : 0; }
@@ -2197,12 +2309,22 @@ static int cholesky_impl(csp_ctx* c, double* x, void* stream, int set, bool li_l
   if (!use_generic(c)) {
     MfmaArgs a0 = mfma_args(c, nullptr, 0, 1);
     a0.LK = nullptr;
-    for (int64_t l = 0; l < c->S.nlev; ++l)
+    auto small = [&](const MfmaArgs& am, int cnt, int thr) {
+      launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)),
+                 (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double), st, am, x, (double*)nullptr);   // compact layout: front + update only
+    };
+    auto large = [&](const MfmaArgs& am, int cnt, int64_t l) {
+      if (use_large() && c->D.gp_tptr) lf_chol(c, am, cnt, x, st, li_last && l == c->S.nlev - 1);
+      else launch_lds(c, KID_chol_mfma_hbm, k_chol_mfma<false>, dim3(cnt), dim3(1024), 0, st, am, x, (double*)nullptr);
+    };
+    // families of the levels 0 / 1 in one launch (front_cholfam.hip); the inverse-form factor is left to prep_lk here
+    const ScalFam sf = scaling_fam_plan(c, a0, set);
+    if (sf.on) scaling_fam_up(c, sf, a0, small, large, [&]() { launch_chol_fam<false>(c, sf, x, (double*)nullptr, st); });
+    for (int64_t l = sf.on ? 2 : 0; l < c->S.nlev; ++l)
       for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t bytes, int thr) {
-        if (lds) launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)),
-                            (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double), st, am, x, (double*)nullptr);   // compact layout: front + update only
-        else if (use_large() && c->D.gp_tptr) lf_chol(c, am, cnt, x, st, li_last && l == c->S.nlev - 1);
-        else launch_lds(c, KID_chol_mfma_hbm, k_chol_mfma<false>, dim3(cnt), dim3(thr), 0, st, am, x, (double*)nullptr);
+        (void)bytes;
+        if (lds) small(am, cnt, thr);
+        else large(am, cnt, l);
       }, set);
   } else
   for_levels_up(c, [&](const int32_t* lev, int cnt) {
@@ -2268,13 +2390,22 @@ static int projected_inverse_impl(csp_ctx* c, double* x, void* stream, int set, 
     // them: no second gather of all Y_AA (four launches, 72 us on synth50k) and no copy (35 us).
     const bool keep_yaa = !set && !cache_off() && c->D.yaa && c->S.updlen() > 0;
     if (keep_yaa) a0.t.upd = c->D.yaa;
-    for (int64_t l = c->S.nlev - 1; l >= 0; --l)
+    auto small = [&](const MfmaArgs& am, int cnt, int thr) {
+      launch_lds(c, KID_pinv_mfma, k_pinv_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 1)),
+                 (size_t)mfma_lds_doubles_for(WK_PINV, am.nnmax, am.namax) * sizeof(double), st, am, x);
+    };
+    auto large = [&](const MfmaArgs& am, int cnt, int64_t) {
+      if (use_large()) lf_pinv(c, am, cnt, x, st);
+      else launch_lds(c, KID_pinv_mfma_hbm, k_pinv_mfma<false>, dim3(cnt), dim3(1024), 0, st, am, x);
+    };
+    const ScalFam sf = scaling_fam_plan(c, a0, set);      // families of the levels 1 / 0 in one launch (front_pinvfam.hip)
+    for (int64_t l = c->S.nlev - 1; l >= (sf.on ? 2 : 0); --l)
       for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t bytes, int thr) {
-        if (lds) launch_lds(c, KID_pinv_mfma, k_pinv_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 1)),
-                            (size_t)mfma_lds_doubles_for(WK_PINV, am.nnmax, am.namax) * sizeof(double), st, am, x);
-        else if (use_large()) lf_pinv(c, am, cnt, x, st);
-        else launch_lds(c, KID_pinv_mfma_hbm, k_pinv_mfma<false>, dim3(cnt), dim3(thr), 0, st, am, x);
+        (void)bytes;
+        if (lds) small(am, cnt, thr);
+        else large(am, cnt, l);
       }, set);
+    if (sf.on) scaling_fam_down(c, sf, a0, small, large, [&]() { launch_pinv_fam(c, sf, a0, x, st); });
     if (keep_yaa) {
       c->D.yaa_tag = x;
       c->D.fac_tag = c->D.faci_tag = nullptr;
@@ -2356,22 +2487,34 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
   static int cprep = -1;
   if (cprep < 0) { const char* e = sw_str("SMCP_CHOL_PREP"); cprep = (e && e[0] == '0') ? 0 : 1; }
   const bool fuse_prep = cprep && nnI <= 16;
+  auto chol_small = [&](const MfmaArgs& am, int cnt, int thr) {
+    const size_t lb = (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double);
+    if (fuse_prep) launch_lds(c, KID_chol_mfma, k_chol_mfma<true, true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, D.lk);
+    else launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, (double*)nullptr);
+  };
+  auto chol_large = [&](const MfmaArgs& am, int cnt, int64_t l) { lf_chol(c, am, cnt, L, st, l == last); };      // (the last level's chain: Li in the same launch where the class allows)
   auto chol_level = [&](int64_t l) {
     for_level_classes(c, l, a0, [&](bool lds, MfmaArgs am, int cnt, size_t bytes, int thr) {
       (void)bytes;
-      const size_t lb = (size_t)mfma_lds_doubles_for(WK_CHOL, am.nnmax, am.namax) * sizeof(double);
-      if (lds && fuse_prep) launch_lds(c, KID_chol_mfma, k_chol_mfma<true, true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, D.lk);
-      else if (lds) launch_lds(c, KID_chol_mfma, k_chol_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 0)), lb, st, am, L, (double*)nullptr);
-      else lf_chol(c, am, cnt, L, st, l == last);      // (the last level's chain: Li in the same launch where the class allows)
+      if (lds) chol_small(am, cnt, thr);
+      else chol_large(am, cnt, l);
     });
   };
+  // the families of the levels 0 / 1 in one launch each way (front_cholfam.hip, front_pinvfam.hip; the family parents are small
+  // cliques of level 1, so both levels lie below the last one and below lstar)
+  const ScalFam sf = scaling_fam_plan(c, a0, 0);
   // ---- 1. cholesky, leaves -> root.  Every cross-stream dependency costs ~10 us of idle stream on this stack (rocprofv3
   // timeline: a gap behind each hipEventRecord / hipStreamWaitEvent), so there are exactly two hand-overs to ONE side stream:
   // before the LAST level's chain (one workgroup for 110 us on synth50k) the side stream takes the inverse-form factor of
   // everything below it and the head of the copy into Y; after the root->leaves pass has left the large-only levels it
   // takes the Cholesky factors of their separator blocks.  The side work is queued AFTER the chain it runs beside, so that
   // the chain's few workgroups are dispatched first.
-  for (int64_t l = 0; l < last; ++l) chol_level(l);
+  if (sf.on)
+    scaling_fam_up(c, sf, a0, chol_small, chol_large, [&]() {
+      if (fuse_prep) launch_chol_fam<true>(c, sf, L, D.lk, st);
+      else launch_chol_fam<false>(c, sf, L, (double*)nullptr, st);
+    });
+  for (int64_t l = sf.on ? 2 : 0; l < last; ++l) chol_level(l);
   std::unique_ptr<Fork> f0;
   if (last > 0) f0.reset(new Fork(c, st, 1));      // (the mark: the filler stream starts behind levels 0 .. last - 1)
   hipStream_t s0 = f0 ? f0->s : st;
@@ -2415,12 +2558,16 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
       }
     });
   };
+  auto pinv_small = [&](const MfmaArgs& am, int cnt, int thr) {
+    launch_lds(c, KID_pinv_mfma, k_pinv_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 1)),
+               (size_t)mfma_lds_doubles_for(WK_PINV, am.nnmax, am.namax) * sizeof(double), st, am, Y);
+  };
+  auto pinv_large = [&](const MfmaArgs& am, int cnt, int64_t) { lf_pinv(c, am, cnt, Y, st); };
   auto pinv_level = [&](int64_t l) {
     for_level_classes(c, l, ap, [&](bool lds, MfmaArgs am, int cnt, size_t bytes, int thr) {
       (void)bytes;
-      if (lds) launch_lds(c, KID_pinv_mfma, k_pinv_mfma<true>, dim3(cnt), dim3(fact_threads(am, thr, 1)),
-                          (size_t)mfma_lds_doubles_for(WK_PINV, am.nnmax, am.namax) * sizeof(double), st, am, Y);
-      else lf_pinv(c, am, cnt, Y, st);
+      if (lds) pinv_small(am, cnt, thr);
+      else pinv_large(am, cnt, l);
     });
   };
   // root -> leaves through the large-only levels (lstar .. last); their Y_AA blocks are then all in yaa and their factors go
@@ -2432,7 +2579,8 @@ static int scaling_impl(csp_ctx* c, double* L, double* Y, int flags, hipStream_t
   std::unique_ptr<Fork> f1;
   if (want_fac && any_large_sep && lstar > 0) f1.reset(new Fork(c, st, 0));
   hipStream_t s1 = f1 ? f1->s : st;
-  for (int64_t l = lstar - 1; l >= 0; --l) pinv_level(l);
+  for (int64_t l = lstar - 1; l >= (sf.on ? 2 : 0); --l) pinv_level(l);
+  if (sf.on) scaling_fam_down(c, sf, ap, pinv_small, pinv_large, [&]() { launch_pinv_fam(c, sf, ap, Y, st); });
   if (want_fac) {
     for (int64_t l = last; l >= lstar; --l) factor_level(l, s1, s1);
     for (int64_t l = lstar - 1; l >= 0; --l) factor_level(l, st, st);

@@ -35,6 +35,7 @@ static const Switch SWITCHES[] = {
   {"SMCP_DOWN_W", "1", "0: k_hess_down_mfma instead of the one-wave k_hess_down_w"},
   {"SMCP_DOWN_FAM", "1", "most right-hand sides of a root -> leaves sweep that take the one-launch family kernel k_hess_down_fam (0: never; the per-level k_hess_down_w launches)"},
   {"SMCP_UP_FAM", "1", "most dense right-hand sides of a leaves -> root sweep that take the resident family kernel k_hess_up_fam1, the level-0 cliques outside the families riding along (0: never; k_hess_up_fam and a launch of their own for those cliques)"},
+  {"SMCP_SCALING_FAM", "1", "0: per-level k_chol_mfma / k_pinv_mfma launches for the families of the scaling point instead of one k_chol_fam / k_pinv_fam launch each way"},
   {"SMCP_FAM", "1", "0: no family kernels (per-level sweeps with the update exchange through HBM)"},
   {"SMCP_FAM2", "1", "0: no sparse-input family kernels (k_fam_sparse, k_fam_terms): k_hess_up_fam"},
   {"SMCP_FAMT", "1", "0: no entry-driven family sweep k_fam_terms (k_fam_sparse instead)"},
