@@ -176,6 +176,31 @@ int csp_symm(csp_ctx* ctx, const double* X, const double* B, int64_t ldb, double
  * listed (clique, 64 panel rows, 256 panel columns) item and one per column of it with a row strictly below.  Host only:
  * needs no device. */
 int64_t csp_symm_positions(csp_ctx* ctx);
+/* Chordal plus low rank: M = L L^T + V diag(a) V^T with V dense n x k (layout of csp_trsm), 1 <= k <= 64, held as the factor
+ * L, W = L^-1 V and a state block of csp_lowrank_state_len(k) doubles on the device: [0] status, [1] sum of log t_j, [2] k,
+ * then a (k), K = W^T W, C, D and S (k x k each, row-major) with
+ *   M = F F^T, F = L (I + W C W^T);  F^-1 = (I + W D W^T) L^-1;  M^-1 = L^-T (I + W S W^T) L^-1;  M = L (I + W A W^T) L^T.
+ * C and D are built one column of V at a time from K and a alone (the columns with a_j > 0 first, then those with a_j < 0,
+ * a_j = 0 skipped), with no division by anything that dependent columns of V make small.  W and the state block belong to the
+ * caller.  All three calls return SMCP_EINVAL for k outside 1 .. 64, a leading dimension below n or a context under a subtree
+ * partition over more than one rank, SMCP_ENODEV without a device.  -1 from csp_lowrank_state_len for k outside 1 .. 64. */
+int64_t csp_lowrank_state_len(int64_t k);
+/* W (ldw >= n) holds V on entry and L^-1 V on return (one csp_trsm); a_host: k coefficients on the HOST, NULL for all ones.
+ * At most three launches beside those of csp_trsm: the slab-wise partial products of K = W^T W and one workgroup for the
+ * k x k construction.  Synchronises the stream and returns 0, or 1 + j when column j (in the caller's order) shows that M is
+ * not positive definite (t_j = 1 + a_j c^T K c <= 0); the state block is then not usable. */
+int csp_lowrank_factor(csp_ctx* ctx, const double* L, double* W, int64_t ldw, int64_t k, const double* a_host, double* state,
+                       void* stream);
+/* B <- op B in place for a dense n x nrhs block B in the layout of csp_trsm (ldb >= n; entries between n and ldb of a column
+ * are not touched).  L, W and the state block are only read.  Exactly two launches (the partial products of W^T B by row
+ * slabs, then B += W (T W^T B) with the partials summed in ascending slab) beside the csp_trsm / csp_trmm launches the
+ * operation wraps, per block of 512 columns; no floating-point atomics, the same arguments give the same bits from call to
+ * call.  Does not synchronise.  Needs the update workspace of csp_trmm / csp_trsm (SMCP_ENOMEM otherwise). */
+enum { CSP_LR_F = 0, CSP_LR_FT = 1, CSP_LR_FINV = 2, CSP_LR_FINVT = 3, CSP_LR_MINV = 4, CSP_LR_M = 5 };
+int csp_lowrank_apply(csp_ctx* ctx, const double* L, const double* W, int64_t ldw, int64_t k, const double* state, double* B,
+                      int64_t ldb, int64_t nrhs, int op, void* stream);
+/* *out (host) = log det M = 2 csp_logdiagsum(L) + sum of log t_j.  Synchronises the stream. */
+int csp_lowrank_logdet(csp_ctx* ctx, const double* L, const double* state, double* out, void* stream);
 /* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
  * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
  * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */

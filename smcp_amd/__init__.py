@@ -9,7 +9,7 @@ from .cspmatrix import cspmatrix  # noqa: F401
 from . import base, solvers  # noqa: F401
 from .base import SDP, band_SDP, mtxnorm_SDP, completion  # noqa: F401  (smcp.__init__: same four names)
 from .base import mrcompletion, maxcut_round, edmcompletion, psdcompletion  # noqa: F401
-from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2k, syrk, syr2, symm, dot, logdiagsum  # noqa: F401
+from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2k, syrk, syr2, symm, dot, logdiagsum, lowrank_factor, LowRankFactor  # noqa: F401
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion
 
 __version__ = "0.1.0"

@@ -39,6 +39,10 @@ SIGNATURES = {
     "csp_syr2k": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_double, ctypes.c_double, c_vp]),
     "csp_symm": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, ctypes.c_double, ctypes.c_double, c_vp]),
     "csp_symm_positions": (c_i64, [c_vp]),
+    "csp_lowrank_state_len": (c_i64, [c_i64]),
+    "csp_lowrank_factor": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "csp_lowrank_apply": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, ctypes.c_int, c_vp]),
+    "csp_lowrank_logdet": (ctypes.c_int, [c_vp, c_vp, c_vp, c_dblp, c_vp]),
     "csp_mrcompletion_rank": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64p, c_vp]),
     "csp_mrcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64, c_vp, c_i64, c_vp]),
     "csp_maxcut_cuts": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

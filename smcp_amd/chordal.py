@@ -328,6 +328,109 @@ def symm(X, B, C=None, alpha=1.0, beta=0.0):
     return C
 
 
+LOWRANK_KMAX = 64
+_LR_OPS = {"F": 0, "FT": 1, "FINV": 2, "FINVT": 3, "MINV": 4, "M": 5}     # include/smcp_amd.h: CSP_LR_*
+
+
+def _lowrank_block(symb, B, what):
+    """The checks of a (kb, n) block of the low-rank calls: ValueError, before the device is touched."""
+    if not isinstance(B, torch.Tensor) or B.dim() != 2:
+        raise ValueError("%s: a 2-D torch tensor of shape (k, n) is needed" % what)
+    if B.shape[0] < 1:
+        raise ValueError("%s: at least one column is needed, got %d" % (what, B.shape[0]))
+    if B.dtype != torch.float64:
+        raise ValueError("%s: float64 is needed, got %s" % (what, B.dtype))
+    if B.shape[1] != symb.n:
+        raise ValueError("%s: %d rows, the pattern has %d" % (what, B.shape[1], symb.n))
+    if B.stride(1) != 1 or (B.shape[0] > 1 and B.stride(0) < symb.n):
+        raise ValueError("%s: stride(1) == 1 and stride(0) >= n are needed" % what)
+    if not B.is_cuda:
+        raise ValueError("%s: a device tensor is needed" % what)
+    return B.stride(0) if B.shape[0] > 1 else max(B.stride(0), symb.n)
+
+
+class LowRankFactor:
+    """M = L L^T + V diag(a) V^T = F F^T held as the chordal factor L, W = L^-1 V and a k x k state on the device
+    (``lowrank_factor``).  F = L (I + W C W^T) is neither triangular nor unique.  All methods work in place on float64
+    device tensors of shape (kb, n), any kb, laid out as for ``trsm`` / ``trmm`` (row r of the tensor is column r of the
+    block, stride(1) == 1, rows in the PERMUTED order; the entries B[r, n:stride(0)] of a padded tensor are not touched).
+    L, W and the state are only read, and the same arguments give the same bits from call to call.
+
+    The object REFERS to L: changing ``L.blkval`` afterwards invalidates it (W and the state were derived from the old
+    factor); build a new one with ``lowrank_factor``."""
+
+    def __init__(self, L, W, state):
+        self.L, self.W, self.state = L, W, state
+        self.k = int(W.shape[0])
+
+    def _apply(self, B, op, what):
+        symb = self.L.symb
+        ldb = _lowrank_block(symb, B, what)
+        if B.device != self.W.device:
+            raise ValueError("%s: B is on %s, the factor on %s" % (what, B.device, self.W.device))
+        _ensure(symb)
+        _fit_workspace(symb, int(symb.sepptr[-1]), min(B.shape[0], 512))
+        _chk(_lib.lib().csp_lowrank_apply(symb.handle, self.L.blkval.data_ptr(), self.W.data_ptr(), self.W.stride(0), self.k,
+                                          self.state.data_ptr(), B.data_ptr(), ldb, B.shape[0], _LR_OPS[op], _stream()), what)
+
+    def trmm(self, B, trans="N"):
+        """B <- F B ('N') or F^T B ('T'; also 1, True)."""
+        self._apply(B, "FT" if trans in ("T", 1, True) else "F", "LowRankFactor.trmm")
+
+    def trsm(self, B, trans="N"):
+        """B <- F^-1 B ('N') or F^-T B ('T'; also 1, True)."""
+        self._apply(B, "FINVT" if trans in ("T", 1, True) else "FINV", "LowRankFactor.trsm")
+
+    def solve(self, B):
+        """B <- M^-1 B."""
+        self._apply(B, "MINV", "LowRankFactor.solve")
+
+    def mul(self, B):
+        """B <- M B."""
+        self._apply(B, "M", "LowRankFactor.mul")
+
+    def logdet(self):
+        """log det M."""
+        out = ctypes.c_double(0.0)
+        _chk(_lib.lib().csp_lowrank_logdet(self.L.symb.handle, self.L.blkval.data_ptr(), self.state.data_ptr(), ctypes.byref(out),
+                                           _stream()), "LowRankFactor.logdet")
+        return out.value
+
+
+def lowrank_factor(L, V, a=None):
+    """The factor of M = L L^T + V diag(a) V^T as a ``LowRankFactor``: L a Cholesky factor on the pattern (as ``cholesky`` /
+    ``completion`` leave it), V a float64 device tensor of shape (k, n), 1 <= k <= 64, with stride(1) == 1, laid out as for
+    ``trsm`` / ``trmm`` (row j is column j of V, rows in the PERMUTED order), a a sequence of k floats (None: all ones; a
+    negative entry is a downdate, a zero entry leaves its column out).  V is not written: the object keeps its own
+    W = L^-1 V, 8 n k bytes beside L, and refers to L.  Nothing n x n is formed.  ValueError for a bad k, shape, dtype or
+    device, raised before the device is touched; ArithmeticError naming the column when M is not positive definite."""
+    symb = L.symb
+    if not isinstance(V, torch.Tensor) or V.dim() != 2:
+        raise ValueError("lowrank_factor: V must be a 2-D torch tensor of shape (k, n)")
+    k = int(V.shape[0])
+    if k < 1 or k > LOWRANK_KMAX:
+        raise ValueError("lowrank_factor: k = %d is outside 1 .. %d" % (k, LOWRANK_KMAX))
+    _lowrank_block(symb, V, "lowrank_factor: V")
+    coef = None
+    if a is not None:
+        coef = [float(x) for x in a]
+        if len(coef) != k or not all(x == x and abs(x) != float("inf") for x in coef):
+            raise ValueError("lowrank_factor: a must hold %d finite numbers" % k)
+    if not L.blkval.is_cuda or L.blkval.device != V.device:
+        raise ValueError("lowrank_factor: L and V must be on the same device")
+    _ensure(symb)
+    lib = _lib.lib()
+    _fit_workspace(symb, int(symb.sepptr[-1]), k)
+    W = V.clone(memory_format=torch.contiguous_format)
+    state = torch.zeros(int(lib.csp_lowrank_state_len(k)), dtype=torch.float64, device=V.device)
+    ah = None if coef is None else (ctypes.c_double * k)(*coef)
+    rc = lib.csp_lowrank_factor(symb.handle, L.blkval.data_ptr(), W.data_ptr(), W.stride(0), k, ah, state.data_ptr(), _stream())
+    if rc > 0:
+        raise ArithmeticError("lowrank_factor: L L^T + V diag(a) V^T is not positive definite (column %d)" % (rc - 1))
+    _chk(rc, "lowrank_factor")
+    return LowRankFactor(L, W, state)
+
+
 def dot(X, Y):
     _ensure(X.symb)
     out = ctypes.c_double(0.0)

@@ -42,6 +42,7 @@
 #include "front_trmm.hip"
 #include "front_syr2k.hip"
 #include "front_symm.hip"
+#include "front_lowrank.hip"
 
 using namespace smcp;
 
@@ -81,6 +82,7 @@ enum {
   KID_qr_dots_many, KID_qr_many_sum, KID_qr_many_small, KID_qr_many_mid, KID_qr_comb_many,
   KID_res_inv_table, KID_res_combine, KID_res_y, KID_res_norms, KID_kkt_many_sub,
   KID_chol_fam, KID_pinv_fam,
+  KID_lr_gram, KID_lr_small, KID_lr_apply,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -107,7 +109,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_potrs_many_small", "k_potrs_many_step", "k_aadj_sub_many", "k_kkt_many_y", "k_kkt_many_scale",
   "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many",
   "k_res_inv_table", "k_res_combine", "k_res_y", "k_res_norms", "k_kkt_many_sub",
-  "k_chol_fam", "k_pinv_fam"};
+  "k_chol_fam", "k_pinv_fam",
+  "k_lr_gram", "k_lr_small", "k_lr_apply"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2692,10 +2695,13 @@ int csp_hessian(csp_ctx* c, const double* L, const double* Y, double* U, int64_t
 
 // Y: the matrix whose pair (L, Y) the cached inverse-form factor may belong to (null: only a factor cached for L itself
 // is reused, otherwise it is formed from L)
-int trsm_impl(csp_ctx* c, const double* L, const double* Y, double* B, int64_t nrhs, int64_t ldb, int trans, hipStream_t st) {
+// fixed_order: the level kernels whatever nrhs (the tile products below add the updates with floating-point atomics: their
+// bits differ from call to call)
+int trsm_impl(csp_ctx* c, const double* L, const double* Y, double* B, int64_t nrhs, int64_t ldb, int trans, hipStream_t st,
+              bool fixed_order = false) {
   static int mm = -1;
   if (mm < 0) { const char* e = sw_str("SMCP_TRSM_MM"); mm = (e && e[0] == '0') ? 0 : 1; }
-  if (mm && !use_generic(c) && use_large() && nrhs >= 8) {
+  if (mm && !fixed_order && !use_generic(c) && use_large() && nrhs >= 8) {
     // tile products with the inverse-form factor (front_large.hip: k_trsm_mm_*): the generic kernels below solve every
     // clique's triangle by substitution in one workgroup per sixteen columns -- 0.48 ms per level on config 4
     if (int rc = prep_lk_cached(c, L, Y, st)) return rc;
@@ -2969,6 +2975,7 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 
 }  // extern "C"
 
+#include "lowrank.hip"
 #include "kkt.hip"
 #include "kkt_many.hip"
 #include "kkt_res_many.hip"

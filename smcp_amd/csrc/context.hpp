@@ -225,6 +225,7 @@ struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
   int64_t fam_maxterms = 0;  // most entries of a (family, constraint) pair: the parent's own + its children's
   double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
   double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
+  double* lr_ws = nullptr; int64_t lr_ws_len = 0;     // partial Gram products of the low-rank factor (lowrank.hip: slabs x k x columns)
   DenseChol chol;
   double* sw = nullptr;      // blklen : sqrt of the inner-product weights (Gram path)
   int lg_rec = 0;                                                     // doubles per child of the per-step tables (lg_tab)

@@ -56,6 +56,7 @@ static const Switch SWITCHES[] = {
   {"SMCP_TRMM_MM", "1", "0: no MFMA tile products in csp_trmm (every front on the FMA kernels); 2: tile products for the large fronts only, also from 32 columns on"},
   {"SMCP_SYR2K_MM", "1", "0: no MFMA tile products in csp_syr2k (every front on the FMA kernel); 2: tile products for the large fronts only, whatever the rank (read on every call)"},
   {"SMCP_SYMM_MM", "1", "0: no MFMA tile products in csp_symm (every front on the FMA kernel); 2: tile products for the large fronts only, whatever the column count (read on every call)"},
+  {"SMCP_LOWRANK_MM", "1", "0: no MFMA tiles in the Gram products of the low-rank factor (k_lr_gram on the FMA route whatever the shape)"},
   {"SMCP_POTRS_MANY_MM", "1", "0: no MFMA tile products in the block steps of dense_potrs_many / kkt_solve_many (FMA updates whatever the column count; read on every call)"},
   {"SMCP_ALDS", "1", "0: extend-add of large fronts by gather plan only (no LDS streaming kernel)"},
   {"SMCP_ALDS_DYN", "1", "0: one workgroup per (front, right-hand side) instead of the task-drawing grid"},
