@@ -34,6 +34,8 @@ typedef struct csp_ctx csp_ctx;
                              CSP_TUNE_VERIFY_CACHE -- a cached quantity is older than the matrix it was derived from */
 #define SMCP_ETIMEOUT (-6) /* a workgroup of the one-launch blocked Cholesky (csrc/front_flow.hip) waited longer than 3 s for a tile
                              of another workgroup: the launch gave up instead of hanging (never seen; the results are invalid) */
+#define SMCP_ENOCONV (-7) /* the Jacobi iteration of csp_clique_eigvalsh did not converge on some clique within 30 sweeps, or the
+                             clique block holds a non-finite entry */
 
 /* ---- symbolic layer (host only, no GPU needed) ------------------------------------- */
 
@@ -78,7 +80,8 @@ enum {
   CSP_Q_MRC_CLAMPED = 18, /* 1 value: cliques of the last csp_mrcompletion on this context whose Schur-complement factor had
                              more pivots above the threshold than the r columns left room for (0 when r came from
                              csp_mrcompletion_rank with the same X and tol, up to rounding) */
-  CSP_Q_EDM_CLAMPED = 19  /* 1 value: the same for the last csp_edmcompletion (r from csp_edmcompletion_rank) */
+  CSP_Q_EDM_CLAMPED = 19, /* 1 value: the same for the last csp_edmcompletion (r from csp_edmcompletion_rank) */
+  CSP_Q_CEIG_SWEEPS = 20  /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh on this context */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -239,6 +242,19 @@ int csp_edm_dense(csp_ctx* ctx, const double* Y, int64_t ldY, int64_t r, const i
  * not positive semidefinite (the test of csp_mrcompletion_rank), SMCP_EINVAL for ldX < n.  X is not changed.
  * Deterministic; synchronises the stream. */
 int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd, int64_t ldX, void* stream);
+/* Spectra of the clique blocks: w[rowptr[k] .. rowptr[k + 1]) (device, rowptr[nsn] doubles) = the eigenvalues, ascending, of
+ * A_gg for clique k = g, or with b given of the pencil (A_gg, B_gg) -- of B_gg^-1 A_gg.  a and b are blkvals read as symmetric
+ * matrices (of a supernode's diagonal block the lower triangle counts) and are not written.  X is in the interior of the
+ * cone of PSD-completable matrices exactly when every X_gg is positive definite, so min w decides membership and
+ * -1 / min w of the pencil (D, X) is the step to the boundary along D.  ext (device, 4 doubles, may be NULL) receives the
+ * smallest eigenvalue over all cliques, the lowest clique attaining it, the largest, and the lowest clique attaining that.
+ * One workgroup per clique: a Cholesky of B_gg and two triangular solves (pencil form), a two-sided cyclic Jacobi in a
+ * fixed parallel order without eigenvectors, a rank sort; at most six launches plus one whatever the tree, beside the
+ * top-down gathers of the separator blocks.  The same input gives the same bits.  Returns 0, 1 + k when B_gg of clique k
+ * is not positive definite, SMCP_ENOCONV when a clique did not converge in 30 sweeps (a non-finite entry ends this way),
+ * SMCP_EINVAL for a null a or w, a replicated context, or w / ext overlapping a, b or each other.  The most sweeps of a
+ * clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back; w and ext are not). */
+int csp_clique_eigvalsh(csp_ctx* ctx, const double* a, const double* b, double* w, double* ext, void* stream);
 /* chompack.dot(X, Y) = tr(XY) on V (solvers.py:399,836,...); result written to *out (host). */
 int csp_dot(csp_ctx* ctx, const double* X, const double* Y, double* out, void* stream);
 /* sum(log(X.diag())) (solvers.py:395,925,934); *out host. */

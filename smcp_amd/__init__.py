@@ -9,7 +9,9 @@ from .cspmatrix import cspmatrix  # noqa: F401
 from . import base, solvers  # noqa: F401
 from .base import SDP, band_SDP, mtxnorm_SDP, completion  # noqa: F401  (smcp.__init__: same four names)
 from .base import mrcompletion, maxcut_round, edmcompletion, psdcompletion  # noqa: F401
+from .base import cone_margin, max_step  # noqa: F401  (scipy matrices; the cspmatrix forms are smcp_amd.chordal.cone_margin / max_step)
 from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2k, syrk, syr2, symm, dot, logdiagsum, lowrank_factor, LowRankFactor  # noqa: F401
+from .chordal import clique_eigvalsh, clique_extremes  # noqa: F401
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion
 
 __version__ = "0.1.0"

@@ -49,7 +49,8 @@ SIGNATURES = {
     "csp_edmcompletion_rank": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64p, c_vp]),
     "csp_edmcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64, c_vp, c_i64, c_vp]),
     "csp_psdcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp]),
-    "csp_edm_dense": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "csp_clique_eigvalsh": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "csp_edm_dense":(ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "csp_dot": (ctypes.c_int, [c_vp, c_vp, c_vp, c_dblp, c_vp]),
     "csp_logdiagsum": (ctypes.c_int, [c_vp, c_vp, c_dblp, c_vp]),
     "csp_axpby": (ctypes.c_int, [c_i64, ctypes.c_double, c_vp, ctypes.c_double, c_vp, c_vp]),

@@ -517,6 +517,50 @@ def edmcompletion(D, tol=1e-12, dense=False):
     return Y.cpu().numpy()[ip]
 
 
+def _on_chordal_pattern(mats, what):
+    """cspmatrices of the sparse symmetric matrices `mats` (scipy sparse, either triangle or both) on the union of their
+    patterns in a perfect elimination order, as edmcompletion embeds its argument; ValueError if that is not chordal."""
+    import torch
+    from .cspmatrix import cspmatrix
+    from .symbolic import Symbolic, maxcardsearch
+    n = sp.csc_matrix(mats[0]).shape[0]
+    ents = []
+    for M in mats:
+        C = sp.coo_matrix(M)
+        if C.shape != (n, n):
+            raise ValueError("%s: the matrices differ in order" % what)
+        low = C.row >= C.col if (C.row > C.col).any() else None
+        if low is not None:
+            ents.append((C.row[low], C.col[low], C.data[low]))
+        else:                                   # upper triangle (or a diagonal matrix) given
+            ents.append((C.col, C.row, C.data))
+    I = np.concatenate([e[0] for e in ents])
+    J = np.concatenate([e[1] for e in ents])
+    pat = sp.csc_matrix((np.ones(len(I)), (I, J)), shape=(n, n)) + sp.identity(n, format="csc")
+    symb = Symbolic(pat, maxcardsearch(pat))
+    if symb.fill > 0:
+        raise ValueError("%s: the pattern is not chordal (%d fill entries)" % (what, symb.fill))
+    dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+    return [cspmatrix.from_entries(symb, i, j, v, device=dev) for i, j, v in ents]
+
+
+def cone_margin(X):
+    """min over the cliques g of lambda_min(X_gg) for the sparse symmetric X (scipy sparse, either triangle or both) on a
+    chordal pattern: X has a positive definite completion exactly when the margin m is positive, and X - t I has one
+    exactly for t < m (smcp_amd.chordal.cone_margin).  ValueError for a pattern that is not chordal."""
+    from . import chordal
+    return chordal.cone_margin(_on_chordal_pattern([X], "cone_margin")[0])[0]
+
+
+def max_step(X, D):
+    """sup{alpha >= 0 : X + alpha D has a positive definite completion} for sparse symmetric X, D (scipy sparse, either
+    triangle or both) whose joint pattern is chordal and X inside the cone; math.inf when no step leaves it
+    (smcp_amd.chordal.max_step).  ValueError for a pattern that is not chordal, ArithmeticError for X outside the cone."""
+    from . import chordal
+    Xc, Dc = _on_chordal_pattern([X, D], "max_step")
+    return chordal.max_step(Xc, Dc)
+
+
 def maxcut_round(P, X, trials=64, seed=0, tol=1e-8):
     """Goemans-Williamson rounding of a max-cut relaxation (maxcut_SDP: C = -(Diag(W 1) - W) / 4) at its solution X
     (scipy sparse, e.g. sol['x']): Y = mrcompletion(X, tol), `trials` Gaussian directions g_t drawn with numpy's

@@ -20,7 +20,8 @@ def _chk(rc, what):
             -1: "invalid argument", -2: "no MI355X device initialised (no CPU fallback)",
             -3: "HIP error", -4: "out of memory",
             -5: "stale derived quantities (prepared sharded factor overwritten, or a matrix changed without csp_touch)",
-            -6: "in-launch dependency wait timed out (one-launch blocked Cholesky)"}.get(rc, "?")))
+            -6: "in-launch dependency wait timed out (one-launch blocked Cholesky)",
+            -7: "the Jacobi iteration of a clique block did not converge in 30 sweeps (a non-finite entry?)"}.get(rc, "?")))
 
 
 def _ensure(symb, nrhs=1):
@@ -185,6 +186,64 @@ def edmcompletion(D, tol=1e-12):
         _chk(L.csp_edmcompletion(symb.handle, D.blkval.data_ptr(), float(tol), r.value, Y.data_ptr(), r.value, _stream()),
              "edmcompletion")
     return Y
+
+
+def _clique_eig(A, B, what):
+    """csp_clique_eigvalsh: (w, ext) as device tensors; ext = [min, its clique, max, its clique]."""
+    symb = A.symb
+    if B is not None and B.symb is not symb:
+        raise ValueError("%s: A and B live on different Symbolics" % what)
+    _ensure(symb)
+    dev = A.blkval.device
+    w = torch.empty(int(symb.rowptr[-1]), dtype=torch.float64, device=dev)
+    ext = torch.empty(4, dtype=torch.float64, device=dev)
+    _chk(_lib.lib().csp_clique_eigvalsh(symb.handle, A.blkval.data_ptr(), None if B is None else B.blkval.data_ptr(),
+                                        w.data_ptr(), ext.data_ptr(), _stream()), what)
+    return w, ext
+
+
+def clique_eigvalsh(A, B=None):
+    """The spectra of the clique blocks: w, a float64 device tensor of length symb.rowptr[-1] whose entries
+    w[rowptr[k]:rowptr[k + 1]] are the eigenvalues, ascending, of A_gg for clique k = g -- with B given, of the pencil
+    (A_gg, B_gg), that is of B_gg^-1 A_gg.  A and B are cspmatrices on the same Symbolic (ValueError otherwise) read as
+    symmetric matrices (of a supernode's diagonal block the lower triangle counts, as ``symm`` reads it); neither is written.
+    ArithmeticError naming the clique when a B_gg is not positive definite, RuntimeError when a clique did not converge in
+    30 Jacobi sweeps (a non-finite entry ends this way).  The same input gives the same bits (csp_clique_eigvalsh)."""
+    return _clique_eig(A, B, "clique_eigvalsh")[0]
+
+
+def clique_extremes(A, B=None):
+    """The (4,) float64 device tensor [smallest eigenvalue over all cliques, lowest clique attaining it, largest eigenvalue,
+    lowest clique attaining that] of ``clique_eigvalsh(A, B)``.  It stays on the device: nothing waits for its values."""
+    return _clique_eig(A, B, "clique_extremes")[1]
+
+
+def clique_eig_sweeps(symb):
+    """The most Jacobi sweeps any clique took in the last ``clique_eigvalsh`` on symb (CSP_Q_CEIG_SWEEPS)."""
+    out = ctypes.c_int64(0)
+    _lib.lib().csp_symbolic_query(symb.handle, 20, ctypes.byref(out))
+    return out.value
+
+
+def cone_margin(X):
+    """(m, clique) with m = min over the cliques g of lambda_min(X_gg), attained at `clique` (the lowest such).  X lies in
+    the interior of the cone C_V of matrices with a positive definite completion exactly when m > 0, and X - t I stays
+    inside exactly for t < m: m is the distance to the boundary along -I, -m the shift that brings an outside X to it."""
+    e = _clique_eig(X, None, "cone_margin")[1].cpu()
+    return float(e[0]), int(e[1])
+
+
+def max_step(X, D, return_clique=False):
+    """sup{alpha >= 0 : X + alpha D in int C_V} for X inside C_V: with mu the smallest eigenvalue over all cliques of the
+    pencils (D_gg, X_gg) it is -1 / mu for mu < 0 and math.inf otherwise.  return_clique=True: (alpha, clique) with the
+    binding clique (the one whose block of X + alpha D is singular; the clique of mu when alpha is inf).  ArithmeticError
+    naming the clique when X is outside the cone (the Cholesky of X_gg inside the pencil), ValueError for different
+    Symbolics.  One ``clique_eigvalsh``: no trial factorisation."""
+    import math
+    e = _clique_eig(D, X, "max_step")[1].cpu()
+    mu = float(e[0])
+    alpha = -1.0 / mu if mu < 0.0 else math.inf
+    return (alpha, int(e[1])) if return_clique else alpha
 
 
 def edm_dense(symb, Y, perm=None):

@@ -39,6 +39,7 @@
 #include "front_mrc.hip"
 #include "front_edm.hip"
 #include "front_psd.hip"
+#include "front_ceig.hip"
 #include "front_trmm.hip"
 #include "front_syr2k.hip"
 #include "front_symm.hip"
@@ -83,6 +84,7 @@ enum {
   KID_res_inv_table, KID_res_combine, KID_res_y, KID_res_norms, KID_kkt_many_sub,
   KID_chol_fam, KID_pinv_fam,
   KID_lr_gram, KID_lr_small, KID_lr_apply,
+  KID_ceig, KID_ceig_reduce,
   KID_COUNT
 };
 const char* const KID_NAMES[KID_COUNT] = {
@@ -110,7 +112,8 @@ const char* const KID_NAMES[KID_COUNT] = {
   "k_stack_dots_many", "k_qr_many_sum", "k_qr_many_small", "k_qr_many_mid", "k_stack_comb_many",
   "k_res_inv_table", "k_res_combine", "k_res_y", "k_res_norms", "k_kkt_many_sub",
   "k_chol_fam", "k_pinv_fam",
-  "k_lr_gram", "k_lr_small", "k_lr_apply"};
+  "k_lr_gram", "k_lr_small", "k_lr_apply",
+  "k_ceig", "k_ceig_reduce"};
 
 // A launch that the runtime refuses (bad configuration, LDS over the limit, ...) must reach the caller: the helpers
 // record the first failure in the context and every entry point ends with end_call(), which returns it.
@@ -2160,6 +2163,9 @@ int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
       return 1;
     case CSP_Q_EDM_CLAMPED:
       if (out) out[0] = c->edm_clamped;
+      return 1;
+    case CSP_Q_CEIG_SWEEPS:
+      if (out) out[0] = c->ceig_sweeps;
       return 1;
   }
   return SMCP_EINVAL;

@@ -1,6 +1,6 @@
 // Host drivers of the completions: minimum-rank (front_mrc.hip, with the cut rounding of csp_maxcut_cuts), Euclidean
-// distance matrix (front_edm.hip, with csp_edm_dense) and dense maximum-determinant PSD (front_psd.hip).  Included by
-// capi.hip.  All three share the launches, slots and per-clique buffers of D.mrc (CompletionWs, context.hpp): a rank pass
+// distance matrix (front_edm.hip, with csp_edm_dense) and dense maximum-determinant PSD (front_psd.hip), and of the
+// spectra of the clique blocks (front_ceig.hip), which run in the same slots.  Included by capi.hip.  All three share the launches, slots and per-clique buffers of D.mrc (CompletionWs, context.hpp): a rank pass
 // over all cliques at once, then either a factor pass, one launch group per level from the root down (mrc, edm), or the
 // solves and fills of the dense completion (psd).
 
@@ -238,6 +238,48 @@ int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t
          Y, ldY, G, s);
   launch(c, KID_cut_weights, k_cut_weights, dim3((unsigned)trials), dim3(MRC_NT), st, n, nedges, ei, ej, w, (const int8_t*)s, cut);
   HIPCHK(end_call(c));
+  return 0;
+}
+
+// ---- spectra of the clique blocks (front_ceig.hip) ------------------------------------------------------------------
+// One launch group over all cliques, as pass 1 of the completions: the separator blocks of A (and of B, into the second
+// gather buffer) gathered top-down, k_ceig by slot size, k_ceig_reduce, and the read-back of its three integers.
+int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w, double* ext, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!a || !w || c->ntrial != 1) return SMCP_EINVAL;
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  const int64_t nsn = S.nsn, wlen = S.rowptr[nsn];
+  auto overlap = [](const double* p, int64_t np, const double* q, int64_t nq) { return p && q && p < q + nq && q < p + np; };
+  for (const double* in : {a, b})
+    if (overlap(w, wlen, in, S.blklen()) || overlap(ext, 4, in, S.blklen())) return SMCP_EINVAL;
+  if (overlap(w, wlen, ext, 4)) return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = mrc_setup(c)) return rc;
+  if (b && !D.mrc.upd2)
+    if (int rc = dev_alloc(&D.mrc.upd2, S.updlen(), D.mem)) return rc;
+  if (!ext && !D.mrc.ext)
+    if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return b ? ceig_slot2(S.nf(k)) : ceig_slot1(S.nf(k)); }, need, ranges, st))
+    return rc;
+  gather_all(c, a, 0, 1, D.upd, st);
+  if (b) gather_all(c, b, 0, 1, D.mrc.upd2, st);
+  MrcArgs m = mrc_args(c, a, 0.0);
+  m.x2 = b;
+  m.upd2 = D.mrc.upd2;
+  m.w = w;
+  if (int rc = mrc_launch<k_ceig>(c, KID_ceig, m, need, 0, nsn, st)) return rc;
+  int32_t* dout = D.mrc.ints + 2 * nsn;
+  launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
+         (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);
+  HIPCHK(end_call(c));
+  int32_t out[3];
+  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->ceig_sweeps = out[2];
+  if (out[0]) return out[0];
+  if (out[1]) return SMCP_ENOCONV;
   return 0;
 }
 

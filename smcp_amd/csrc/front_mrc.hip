@@ -46,6 +46,9 @@ struct MrcArgs {
   double* pw;               // k_psd_solve (front_psd.hip): W_k[rho] of every clique, A[rho], |rho|
   int32_t* pidx;
   int32_t* pra;
+  const double* x2;         // k_ceig (front_ceig.hip): blkval of B and B_AA of every clique (null: standard form), the
+  const double* upd2;       // eigenvalues of clique k at w + cl[k].rows
+  double* w;
 };
 
 // (value, index) of the largest val(i), i < n; ties go to the lowest index, -1 when every value is -inf / NaN.  The
