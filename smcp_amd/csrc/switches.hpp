@@ -1,8 +1,11 @@
 // Every environment switch of the library in ONE table: name, default, meaning.  Every site reads its switch through this
 // table (sw_str / sw_on / sw_int: the only getenv of the library), and a variable SMCP_* found in the environment that the table
 // does not know is reported on stderr once per process (a mistyped switch would otherwise be silently ignored).  Defaults are the production
-// routes; everything else exists for A/B measurements (DESIGN.md section 3 quotes the numbers) and for the parity suite,
-// which runs the fallback routes through them.  SMCP_BENCH_* belong to bench.py, SMCP_CXXFLAGS / SMCP_STAMPS to the build.
+// routes; everything else exists for A/B measurements (DESIGN.md section 3 quotes the numbers) and for the route ledger
+// (tests/route_ledger.py, tests/test_gpu_route_ledger.py), which runs every switch of the "routes" section off its default in a
+// child interpreter, against the dense definitions and with the launch counts that show the switch taking effect: a new route
+// switch must enter that ledger (a test that runs on a CPU reads this section and says so).  SMCP_BENCH_* belong to bench.py,
+// SMCP_CXXFLAGS / SMCP_STAMPS to the build.
 #pragma once
 #include <cstdio>
 #include <cstdlib>

@@ -111,6 +111,7 @@ class DenseCase:
         self.Ablk = S.project(self.proj(self.A))
         self.Yblk = S.project(self.proj(self.Ai))
         self._kkt = None
+        self.kkt_recipe = (KKT_M, KKT_DENSITY, KKT_SEED)    # (m, density, seed); tests/route_ledger.py sets its own before kkt()
 
     def proj(self, M):
         return np.where(self.mask, M, 0.0)
@@ -143,7 +144,8 @@ class DenseCase:
     def kkt(self):
         if self._kkt is None:
             S = self.S
-            cptr, cidx, cval = problems.random_constraints(self.lay, KKT_M, density=KKT_DENSITY, seed=KKT_SEED)
+            m, density, seed = self.kkt_recipe
+            cptr, cidx, cval = problems.random_constraints(self.lay, m, density=density, seed=seed)
             K = orc.KKT(S, cptr, cidx, cval)
             Ad = [S.dense(K.constraint(j)) for j in range(K.m)]
             W = [self.Ai @ Aj @ self.Ai for Aj in Ad]
