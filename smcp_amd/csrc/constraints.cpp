@@ -304,6 +304,12 @@ bool number_families(Build& B) {
 // launch from the entry lists (front_famt.hip, header): own entry v at (i, j): e_i, e_j, v (v / 2 on the diagonal); child
 // entry at (separator row a, column j): q~_{c,j}, e_{rel_c[a]}, -v; child entry at (i, j) of its supernode block: q~_{c,i},
 // q~_{c,j}, v (v / 2).  Sizes first, then the lists themselves, the families spread over host threads.
+// A term with exactly one unit vector of the parent's separator part (id < famt_child and >= nn of the parent: an own entry in a
+// separator row, a child's separator-row entry whose row lands there) is a UNIT term: a(e_i) is a unit vector, so the term adds
+// s a(d) to one row and column of the update and needs no matrix product.  Every list holds its dense terms first, then its
+// unit terms, each class in the entry order above; a unit term carries FAM_UNIT_TERM, its dense vector in the low half and
+// its unit vector in the high half (ids are below 256).  The same constant is FAMT_UNIT of front_famt.hip.
+constexpr int32_t FAM_UNIT_TERM = 1 << 30;
 void family_term_lists(Build& B) {
   const Symbolic& S = B.S;
   ConstraintTables& T = B.T;
@@ -335,27 +341,43 @@ void family_term_lists(Build& B) {
   T.fsv.resize((size_t)run);
   const int nth = B.threads = host_threads(B.P.max_threads, nfam / 16 + 1);
   run_threads(nth, [&](int tix) {
+    std::vector<int32_t> upk;          // the unit terms of the list being written, in entry order
+    std::vector<double> usv;
     for (int64_t f = tix; f < nfam; f += nth) {
       const int64_t k = fam_k[(size_t)f];
+      const int32_t nnp = (int32_t)S.nn(k);
       for (int64_t j = 0; j < m; ++j) {
         size_t o = (size_t)fptr[(size_t)f * (m + 1) + j];
-        for (int32_t q = kptr[(size_t)k * (m + 1) + j]; q < kptr[(size_t)k * (m + 1) + j + 1]; ++q, ++o) {
+        upk.clear();
+        usv.clear();
+        // vx, vy as the mapping above gives them: dense terms go to the list at once, unit terms behind them
+        auto put = [&](int32_t vx, int32_t vy, double s) {
+          const bool ux = vx < CHILD && vx >= nnp, uy = vy < CHILD && vy >= nnp;
+          if (ux != uy) {
+            upk.push_back((ux ? vy | (vx << 16) : vx | (vy << 16)) | FAM_UNIT_TERM);
+            usv.push_back(s);
+          } else {
+            T.fpk[o] = vx | (vy << 16);
+            T.fsv[o++] = s;
+          }
+        };
+        for (int32_t q = kptr[(size_t)k * (m + 1) + j]; q < kptr[(size_t)k * (m + 1) + j + 1]; ++q) {
           const int32_t i = kij[q] & 0xffff, jc = kij[q] >> 16;
-          T.fpk[o] = i | (jc << 16);
-          T.fsv[o] = i == jc ? 0.5 * kval[q] : kval[q];
+          put(i, jc, i == jc ? 0.5 * kval[q] : kval[q]);
         }
         int32_t colbase = 0;
         for (int64_t q2 = S.chptr[k]; q2 < S.chptr[k + 1]; ++q2) {
           const int64_t cc = S.chidx[q2];
           const int32_t nnc = (int32_t)S.nn(cc);
           const int32_t* rel = &S.relidx[S.sepptr[cc]];
-          for (int32_t q = kptr[(size_t)cc * (m + 1) + j]; q < kptr[(size_t)cc * (m + 1) + j + 1]; ++q, ++o) {
+          for (int32_t q = kptr[(size_t)cc * (m + 1) + j]; q < kptr[(size_t)cc * (m + 1) + j + 1]; ++q) {
             const int32_t i = kij[q] & 0xffff, jc = kij[q] >> 16;
-            if (i >= nnc) { T.fpk[o] = (CHILD + colbase + jc) | (rel[i - nnc] << 16); T.fsv[o] = -kval[q]; }
-            else { T.fpk[o] = (CHILD + colbase + i) | ((CHILD + colbase + jc) << 16); T.fsv[o] = i == jc ? 0.5 * kval[q] : kval[q]; }
+            if (i >= nnc) put(CHILD + colbase + jc, rel[i - nnc], -kval[q]);
+            else put(CHILD + colbase + i, CHILD + colbase + jc, i == jc ? 0.5 * kval[q] : kval[q]);
           }
           colbase += nnc;
         }
+        for (size_t x = 0; x < upk.size(); ++x, ++o) { T.fpk[o] = upk[x]; T.fsv[o] = usv[x]; }
       }
     }
   });

@@ -74,6 +74,12 @@ constexpr int FAMT_HDR = 32;        // doubles: the header of a record (ints, as
 constexpr int FAMT_TCAP = 96;       // ordered pairs t' per (parent, right-hand side): 48 entries (host-checked)
 constexpr int FAMT_TMAX = 384;      // longest (family, constraint) list the entry-driven sweeps take (in chunks of FAMT_TCAP / 2; host-checked)
 constexpr int FAMT_CHILD = 128;     // vector ids: < 128 unit vector e_id of the parent's front, >= 128 child column id - 128
+constexpr int FAMT_UNIT = 1 << 30;  // static term lists (constraints.cpp, FAM_UNIT_TERM): a term with exactly one unit vector of the
+                                    // separator part -- dense vector id in bits 0-7, unit vector id in bits 16-23
+#ifndef SMCP_FAMT_UB
+#define SMCP_FAMT_UB 8
+#endif
+constexpr int FAMT_UB = SMCP_FAMT_UB;   // unit terms of lf_add_family whose loads are in flight together
 
 // LDS of k_famt_prep (doubles): R^T | -K | Li | per wave q~ (16 + NA) and the a images of its child's columns (cnn x NA)
 template <int NAT>
@@ -515,16 +521,59 @@ __device__ inline void lf_add_family(double* T, int nf, const MfmaArgs& a, int z
   const double* const tab = a.fz_tab + (int64_t)slot * a.fz_recl + FAMT_HDR;
   // (a list of more than 64 terms -- one per lane -- is taken in chunks of 64, the accumulators persist)
   const int pbase = (int)(uint32_t)(pt & 0xffffffffll), Ttot = min((int)(pt >> 32), FAMT_TMAX);
-  int relv[NAT];
+  // rel by lane: lane p holds the front row of row p of the update (NA <= 64; the lanes beyond na repeat the last row's) -- the
+  // unit terms use it as it is, the scatter of the tiles takes its rows and columns from it by cross-lane reads
+  const int rell = rel[min(lane, max(nap - 1, 0))];
+  // the terms of a chunk, one per lane: its dense terms on the lanes 0 .. Td - 1, its unit terms behind them (the host orders
+  // every list so); returns Td
+  int pk = 0;
+  double sv = 0.0;
+  auto load = [&](const int p0, const int Tn) {
+    pk = 0; sv = 0.0;
+    if (lane < Tn) { pk = a.fz_pk[p0 + lane]; sv = a.fz_s[p0 + lane]; }
+    return (int)__popcll(__ballot(lane < Tn && !(pk & FAMT_UNIT)));
+  };
+  // Unit terms s (a_d e_u^T + e_u a_d^T) of the lanes Td .. Tn - 1: s a_d goes to row and column u of the update, i.e. one
+  // ds_add_f64 per lane (lane p = row p; (u, u) gets it twice) at the front position of (rel[p], rel[u]) -- no product.  The
+  // descriptor of a term is wave-uniform (read from its lane); the 512-byte loads of FAMT_UB terms are requested together.
+  auto units = [&](const int Td, const int Tn) {
+    for (int t0 = Td; t0 < Tn; t0 += FAMT_UB) {
+      double av[FAMT_UB];
+      int pkt[FAMT_UB];
 #pragma unroll
-  for (int t = 0; t < NAT; ++t) relv[t] = rel[min(16 * t + l15, max(nap - 1, 0))];
+      for (int g = 0; g < FAMT_UB; ++g) {                      // (unconditional requests at a clamped term, as in the dense steps)
+        pkt[g] = __builtin_amdgcn_readlane(pk, min(t0 + g, Tn - 1));
+        const int vd = pkt[g] & 0xff;
+        const int ad = vd >= FAMT_CHILD ? L.oCA + NA * (vd - FAMT_CHILD) : L.onK + NA * vd;
+        av[g] = tab[ad + min(lane, NA - 1)];
+      }
+      const famt_u2 sw = __builtin_bit_cast(famt_u2, sv);
+#pragma unroll
+      for (int g = 0; g < FAMT_UB; ++g)
+        if (t0 + g < Tn) {
+          const int u = (((pkt[g] >> 16) & 0xff) - nnp) & 63;
+          const famt_u2 sl = {(unsigned)__builtin_amdgcn_readlane((int)sw.x, t0 + g), (unsigned)__builtin_amdgcn_readlane((int)sw.y, t0 + g)};
+          const double s = __builtin_bit_cast(double, sl);
+          const int fu = __builtin_amdgcn_readlane(rell, u);
+          const int cj = min(rell, fu), ri = max(rell, fu);
+          if (lane < nap) unsafeAtomicAdd(&T[cj * nf - ((cj * (cj - 1)) >> 1) - cj + ri], (lane == u ? 2.0 : 1.0) * s * av[g]);
+        }
+    }
+  };
+  // The unit terms of the whole list first: the ten accumulator tiles are not alive yet.  Td then counts the dense terms of
+  // the list -- its first Td terms.
+  int Td = 0;
+  for (int c0 = 0; c0 < Ttot; c0 += 64) {
+    const int Tn = min(64, Ttot - c0), Tdc = load(pbase + c0, Tn);
+    units(Tdc, Tn);
+    Td += Tdc;
+  }
+  if (Td == 0) return;                                         // nothing for the matrix pipe: no accumulators, no scatter
   d4 acc[NTU];
 #pragma unroll
   for (int x = 0; x < NTU; ++x) acc[x] = d4{0.0, 0.0, 0.0, 0.0};
-  auto chunk = [&](const int p0, const int Tn) {
-  int pk = 0;
-  double sv = 0.0;
-  if (lane < Tn) { pk = a.fz_pk[p0 + lane]; sv = a.fz_s[p0 + lane]; }
+  // dense terms of a chunk: pk, sv hold them on the lanes 0 .. Tn - 1 and zeros beyond
+  auto chunk = [&](const int Tn) {
   const int ks = (2 * Tn + 3) >> 2;
   // operands of step s: the a images of the two vectors of ordered pair tp = kq + 4 s (entry tp >> 1 taken as (x, y) or (y, x)).
   // The two ordered pairs of an entry sit sixteen lanes apart (kq even / odd) and want the same two images with the roles
@@ -534,7 +583,7 @@ __device__ inline void lf_add_family(double* T, int nf, const MfmaArgs& a, int z
     const int tp = kq + 4 * s, e = tp >> 1;
     const int pke = __shfl(pk, e, 64);
     se = __shfl(sv, e, 64);                                  // (lanes beyond the list hold a zero scale)
-    const int v0 = pke & 0xffff, v1 = (pke >> 16) & 0xffff;
+    const int v0 = pke & 0xff, v1 = (pke >> 16) & 0xff;
     const int vx = (tp & 1) ? v1 : v0, vy = (tp & 1) ? v0 : v1;
     // a image of a vector id: offset in the record and the index of its unit part (255: none)
     ux = (vx < FAMT_CHILD && vx >= nnp) ? vx - nnp : 255;
@@ -584,10 +633,20 @@ __device__ inline void lf_add_family(double* T, int nf, const MfmaArgs& a, int z
     }
   }
   };
-  // (the usual list is one chunk: straight-line, as before the chunks existed -- the kernel runs at its register limit)
-  if (Ttot <= 64) chunk(pbase, Ttot);
-  else for (int c0 = 0; c0 < Ttot; c0 += 64) chunk(pbase + c0, min(64, Ttot - c0));
+  // (the usual list is one chunk: straight-line, as before the chunks existed -- the kernel runs at its register limit; its
+  // terms are in pk, sv already, the unit terms among them are blanked)
+  if (Ttot <= 64) {
+    if (lane >= Td) { pk = 0; sv = 0.0; }
+    chunk(Td);
+  } else for (int c0 = 0; c0 < Td; c0 += 64) {
+    const int Tn = min(64, Td - c0);
+    load(pbase + c0, Tn);
+    chunk(Tn);
+  }
   // element (m, n) of the update -> front position (rel[m], rel[n]); packed column start minus the column index as in lf_alds_task
+  int relv[NAT];                                                // (in the tiles' layout: row 16 t + l15)
+#pragma unroll
+  for (int t = 0; t < NAT; ++t) relv[t] = __shfl(rell, 16 * t + l15, 64);
 #pragma unroll
   for (int rt = 0; rt < NAT; ++rt) {
     const int m = 16 * rt + l15;
