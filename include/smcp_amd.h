@@ -255,6 +255,37 @@ int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd
  * SMCP_EINVAL for a null a or w, a replicated context, or w / ext overlapping a, b or each other.  The most sweeps of a
  * clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back; w and ext are not). */
 int csp_clique_eigvalsh(csp_ctx* ctx, const double* a, const double* b, double* w, double* ext, void* stream);
+/* Lanczos on the dual cone: the extreme Ritz values of L^-1 D L^-T (D a blkval read as csp_symm reads it; -1 / theta_min is
+ * the step at which L L^T + alpha D stops being positive definite) or, with D NULL, of L^-T L^-1 (1 / theta_max is the
+ * smallest eigenvalue of L L^T), with full reorthogonalisation (classical Gram-Schmidt twice) and no host round trip per step.
+ * The workspace belongs to the caller: csp_lanczos_work_len(n, jmax) doubles on the device (host only; -1 for n < 1 or jmax
+ * outside 1 .. 128), laid out as
+ *   the state block, 16 + 2 jmax + 1 doubles rounded up to a multiple of 8: [0] status (0 running, 1 the iteration broke
+ *     down: the Krylov space is invariant and the Ritz values are eigenvalues, 2 a non-finite alpha or beta), [1] steps done m,
+ *     [2] the step count at which it broke down (-1: never), [3] the pending scale, [4 .. 7] theta_min, resid_min, theta_max,
+ *     resid_max, [8] max(|alpha|, beta) seen so far, [16 + j] alpha_j, [16 + jmax + j] beta_j (beta_0 = |v0|);
+ *   the partial sums of the two Gram-Schmidt passes (2 x 128 x jmax, each rounded up to a multiple of 8) and of |w|^2
+ *     (ceil(n / 256), rounded up likewise);
+ *   the basis: rows v_0 .. v_jmax of ld = n rounded up to a multiple of 8 doubles (entries n .. ld of a row are not touched);
+ *   two scratch rows of ld doubles.
+ * csp_lanczos_steps runs steps j0 .. j0 + nsteps - 1 (j0 + nsteps <= jmax).  Before j0 = 0 the caller puts v0 into basis row 0;
+ * the call normalises it and resets the state block.  Step j applies the operator to v_j (csp_trsm, csp_symm, csp_trsm on one
+ * column, or csp_trsm twice: those calls' own launches), orthogonalises the result against v_0 .. v_j, stores alpha_j and
+ * beta_{j+1} and writes v_{j+1}; beta_{j+1} <= n eps max(|alpha|, beta seen so far) is a breakdown: status 1, v_{j+1} and
+ * everything after it exact zeros, later steps of the call count nothing and stay finite.  Seven launches per step beside the
+ * operator's, three more at j0 = 0; every sum in a fixed order, no floating-point atomics: the same input gives the same bits.
+ * Does not synchronise and reads nothing back.  L and D are not written.  Needs the update workspace of csp_trsm and csp_symm
+ * for one column (SMCP_ENOMEM otherwise).  SMCP_EINVAL for a null L or work, jmax outside 1 .. 128, a step range outside
+ * 0 .. jmax, a replicated context or one under a subtree partition over more than one rank; SMCP_ENODEV without a device. */
+int64_t csp_lanczos_work_len(int64_t n, int64_t jmax);
+int csp_lanczos_steps(csp_ctx* ctx, const double* L, const double* D, double* work, int64_t jmax, int64_t j0, int64_t nsteps,
+                      void* stream);
+/* From alpha_0 .. alpha_{m-1}, beta_1 .. beta_m of the m steps done so far: the extreme eigenvalues theta_min, theta_max of the
+ * tridiagonal T_m to eps |T_m| (multisection by Sturm counts from the Gershgorin interval, eight rounds of 128 shifts per
+ * end) and the residual estimates beta_m |bottom component of the normalised eigenvector| (two steps of inverse iteration
+ * with a pivoted tridiagonal solve), left in the state block.  m = 1: alpha_0 and beta_1.  One launch of one workgroup; the
+ * same input gives the same bits.  Does not synchronise. */
+int csp_lanczos_ritz(csp_ctx* ctx, double* work, int64_t jmax, void* stream);
 /* chompack.dot(X, Y) = tr(XY) on V (solvers.py:399,836,...); result written to *out (host). */
 int csp_dot(csp_ctx* ctx, const double* X, const double* Y, double* out, void* stream);
 /* sum(log(X.diag())) (solvers.py:395,925,934); *out host. */

@@ -10,6 +10,7 @@ from . import base, solvers  # noqa: F401
 from .base import SDP, band_SDP, mtxnorm_SDP, completion  # noqa: F401  (smcp.__init__: same four names)
 from .base import mrcompletion, maxcut_round, edmcompletion, psdcompletion  # noqa: F401
 from .base import cone_margin, max_step  # noqa: F401  (scipy matrices; the cspmatrix forms are smcp_amd.chordal.cone_margin / max_step)
+from .base import dual_max_step, dual_margin  # noqa: F401  (scipy matrices; the cspmatrix forms are smcp_amd.chordal.dual_max_step / dual_margin)
 from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2k, syrk, syr2, symm, dot, logdiagsum, lowrank_factor, LowRankFactor  # noqa: F401
 from .chordal import clique_eigvalsh, clique_extremes  # noqa: F401
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion

@@ -50,6 +50,9 @@ SIGNATURES = {
     "csp_edmcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64, c_vp, c_i64, c_vp]),
     "csp_psdcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_vp, c_i64, c_vp]),
     "csp_clique_eigvalsh": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "csp_lanczos_work_len": (c_i64, [c_i64, c_i64]),
+    "csp_lanczos_steps": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "csp_lanczos_ritz": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),
     "csp_edm_dense":(ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "csp_dot": (ctypes.c_int, [c_vp, c_vp, c_vp, c_dblp, c_vp]),
     "csp_logdiagsum": (ctypes.c_int, [c_vp, c_vp, c_dblp, c_vp]),

@@ -561,6 +561,29 @@ def max_step(X, D):
     return chordal.max_step(Xc, Dc)
 
 
+def dual_max_step(S, D, tol=1e-10, maxit=64):
+    """sup{alpha >= 0 : S + alpha D is positive definite} for sparse symmetric S, D (scipy sparse, either triangle or both)
+    whose joint pattern is chordal and S positive definite; math.inf when no step leaves the cone: ``cholesky`` of S, then
+    smcp_amd.chordal.dual_max_step (a Lanczos estimate that is never below the true step; read its docstring for what is
+    and is not guaranteed).  ValueError for a pattern that is not chordal, ArithmeticError (that of ``cholesky``) when S is
+    not positive definite."""
+    from . import chordal
+    Sc, Dc = _on_chordal_pattern([S, D], "dual_max_step")
+    chordal.cholesky(Sc)
+    return chordal.dual_max_step(Sc, Dc, tol=tol, maxit=maxit)
+
+
+def dual_margin(S, tol=1e-10, maxit=64):
+    """The smallest eigenvalue of the sparse symmetric positive definite S (scipy sparse, either triangle or both) on a
+    chordal pattern: S - t I stays positive definite exactly for t below it (``cholesky`` of S, then
+    smcp_amd.chordal.dual_margin).  ValueError for a pattern that is not chordal, ArithmeticError (that of ``cholesky``)
+    when S is not positive definite."""
+    from . import chordal
+    Sc = _on_chordal_pattern([S], "dual_margin")[0]
+    chordal.cholesky(Sc)
+    return chordal.dual_margin(Sc, tol=tol, maxit=maxit)
+
+
 def maxcut_round(P, X, trials=64, seed=0, tol=1e-8):
     """Goemans-Williamson rounding of a max-cut relaxation (maxcut_SDP: C = -(Diag(W 1) - W) / 4) at its solution X
     (scipy sparse, e.g. sol['x']): Y = mrcompletion(X, tol), `trials` Gaussian directions g_t drawn with numpy's

@@ -246,6 +246,131 @@ def max_step(X, D, return_clique=False):
     return (alpha, int(e[1])) if return_clique else alpha
 
 
+LANCZOS_JMAX = 128    # csrc/front_lanczos.hip: LZ_JMAX
+LANCZOS_CHUNK = 8     # steps between two looks at the Ritz values
+_LANCZOS_SEED = 20240607
+
+
+def lanczos_maxit(n, maxit):
+    """The Krylov dimension a call may reach: maxit clamped to 1 .. min(n, LANCZOS_JMAX)."""
+    return max(1, min(int(maxit), int(n), LANCZOS_JMAX))
+
+
+def lanczos_chunks(jmax, chunk=LANCZOS_CHUNK):
+    """[(j0, nsteps)] of the calls of csp_lanczos_steps up to dimension jmax: chunks of `chunk`, the last one shorter."""
+    return [(j0, min(chunk, jmax - j0)) for j0 in range(0, jmax, chunk)]
+
+
+def lanczos_layout(n, jmax):
+    """(state length, offset of basis row 0, row stride, total length) of the workspace of csp_lanczos_steps in doubles
+    (include/smcp_amd.h)."""
+    up8 = lambda x: (x + 7) & ~7
+    state = up8(16 + 2 * jmax + 1)
+    basis = state + 2 * up8(128 * jmax) + up8(-(-n // 256))
+    ld = up8(n)
+    return state, basis, ld, basis + (jmax + 3) * ld
+
+
+def lanczos_default_v0(n):
+    """The start vector used when none is given: standard normal from a fixed seed, made on the host."""
+    import numpy as np
+    return np.random.default_rng(_LANCZOS_SEED).standard_normal(n)
+
+
+def lanczos_converged(resid, theta_min, theta_max, tol, steps, n, invariant):
+    """The stopping rule: the residual estimate of the wanted end is below tol max(|theta_min|, |theta_max|), or the Krylov
+    space is exhausted (steps == n) or invariant (the iteration broke down)."""
+    return bool(invariant or steps >= n or resid <= tol * max(abs(theta_min), abs(theta_max)))
+
+
+def lanczos_extremes(L, D=None, tol=1e-10, maxit=64, v0=None, which="min", return_work=False):
+    """The extreme Ritz values of L^-1 D L^-T (D a cspmatrix on the Symbolic of L, read as symmetric exactly as ``symm`` reads
+    it) or, with D None, of L^-T L^-1 = (L L^T)^-1, by Lanczos with full reorthogonalisation on the device
+    (csp_lanczos_steps / csp_lanczos_ritz): chunks of eight steps, then one look at the four numbers of the state block.
+    Returns a dict: theta_min, theta_max, resid_min, resid_max (the estimates beta_j |bottom component of the Ritz vector|),
+    steps, invariant (the iteration broke down: the Ritz values are eigenvalues), converged (``lanczos_converged`` for the end
+    named by `which`, 'min' or 'max').  maxit is clamped to min(n, LANCZOS_JMAX); v0 is a start vector of length n in the
+    PERMUTED order (sequence, numpy array or tensor; default ``lanczos_default_v0``).  The same inputs give the same bits.
+    L and D are not written.  ValueError for different Symbolics or a v0 of the wrong length."""
+    import numpy as np
+    symb = L.symb
+    if D is not None and D.symb is not symb:
+        raise ValueError("lanczos_extremes: L and D live on different Symbolics")
+    if which not in ("min", "max"):
+        raise ValueError("lanczos_extremes: which must be 'min' or 'max'")
+    n = int(symb.n)
+    if v0 is None:
+        v0 = lanczos_default_v0(n)
+    if isinstance(v0, torch.Tensor):
+        v0t = v0.detach().to(dtype=torch.float64).reshape(-1)
+    else:
+        v0t = torch.from_numpy(np.ascontiguousarray(np.asarray(v0, dtype=np.float64).reshape(-1)))
+    if v0t.numel() != n:
+        raise ValueError("lanczos_extremes: v0 has %d entries, the pattern has %d rows" % (v0t.numel(), n))
+    _ensure(symb)
+    lib = _lib.lib()
+    _fit_workspace(symb, int(symb.sepptr[-1]), 1)
+    if D is not None:
+        _fit_workspace(symb, int(lib.csp_symm_positions(symb.handle)), 1)
+    jmax = lanczos_maxit(n, maxit)
+    state_len, basis, ld, total = lanczos_layout(n, jmax)
+    assert total == int(lib.csp_lanczos_work_len(n, jmax))
+    dev = L.blkval.device
+    work = torch.zeros(total, dtype=torch.float64, device=dev)
+    work[basis:basis + n].copy_(v0t)
+    h, Lp, Dp, wp = symb.handle, L.blkval.data_ptr(), None if D is None else D.blkval.data_ptr(), work.data_ptr()
+    info = None
+    for j0, ns in lanczos_chunks(jmax):
+        _chk(lib.csp_lanczos_steps(h, Lp, Dp, wp, jmax, j0, ns, _stream()), "lanczos_extremes")
+        _chk(lib.csp_lanczos_ritz(h, wp, jmax, _stream()), "lanczos_extremes")
+        s = work[:8].cpu().tolist()                  # the one read-back of a chunk: status, steps and the four outputs
+        if s[0] == 2.0:
+            raise RuntimeError("lanczos_extremes: a non-finite value at step %d (is L a Cholesky factor?)" % int(s[2]))
+        info = {"theta_min": s[4], "resid_min": s[5], "theta_max": s[6], "resid_max": s[7], "steps": int(s[1]),
+                "invariant": s[0] == 1.0}
+        info["converged"] = lanczos_converged(info["resid_" + which], s[4], s[6], tol, info["steps"], n, info["invariant"])
+        if info["converged"]:
+            break
+    if return_work:
+        info["work"], info["jmax"] = work, jmax
+    return info
+
+
+def dual_max_step(L, D, tol=1e-10, maxit=64, v0=None, return_info=False):
+    """sup{alpha >= 0 : L L^T + alpha D is positive definite} for the factor L that ``cholesky`` leaves and a direction D on
+    the same Symbolic (ValueError otherwise), read as symmetric exactly as ``symm`` reads it: -1 / theta_min when the
+    smallest Ritz value theta_min of L^-1 D L^-T is negative, math.inf otherwise (``lanczos_extremes``).  return_info=True:
+    (alpha, info) with info the dict of ``lanczos_extremes`` plus alpha_safe = -1 / (theta_min - resid_min), or inf.
+
+    What is rigorous: Ritz values lie inside the spectrum, so theta_min is never below the smallest eigenvalue and the
+    returned alpha is never BELOW the true step, up to rounding -- it is an upper estimate that decreases to the step as the
+    iteration converges.  What is not: alpha_safe is a lower bound of the step only once theta_min has converged to the
+    SMALLEST eigenvalue (then that eigenvalue is no further than resid_min below theta_min); the residual estimate says
+    that a Ritz pair has converged to SOME eigenvalue, which indicates but does not prove it, and `converged` reports only
+    that estimate.  A caller who needs a guarantee takes a fraction of alpha_safe or confirms it with one ``cholesky``."""
+    import math
+    info = lanczos_extremes(L, D, tol, maxit, v0, "min")
+    th = info["theta_min"]
+    alpha = -1.0 / th if th < 0.0 else math.inf
+    lo = th - info["resid_min"]
+    info["alpha_safe"] = -1.0 / lo if lo < 0.0 else math.inf
+    return (alpha, info) if return_info else alpha
+
+
+def dual_margin(L, tol=1e-10, maxit=64, v0=None, return_info=False):
+    """lambda_min(L L^T) for the factor L that ``cholesky`` leaves, as 1 / theta_max of L^-T L^-1 (``lanczos_extremes``
+    without D): S = L L^T is positive definite, and S - t I stays so exactly for t < margin -- the dual counterpart of
+    ``cone_margin``.  return_info=True: (margin, info) with info the dict of ``lanczos_extremes`` (converged refers to
+    theta_max) plus cond = theta_max / theta_min, the Ritz estimate of the condition number of S (1 / theta_min estimates
+    lambda_max(S)).  theta_max is never above the largest eigenvalue of S^-1, so the margin returned is never below the
+    true one, up to rounding; 1 / (theta_max + resid_max) is a lower bound only once theta_max has converged to the largest
+    eigenvalue, which the residual estimate indicates and does not prove."""
+    info = lanczos_extremes(L, None, tol, maxit, v0, "max")
+    margin = 1.0 / info["theta_max"]
+    info["cond"] = info["theta_max"] / info["theta_min"]
+    return (margin, info) if return_info else margin
+
+
 def edm_dense(symb, Y, perm=None):
     """The completed EDM as a dense n x n device tensor: D[i, j] = |Y[p_i] - Y[p_j]|^2 (csp_edm_dense) for Y of
     edmcompletion, p = perm (int64 device tensor of row indices of Y; None: the identity, the permuted order)."""

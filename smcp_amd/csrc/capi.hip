@@ -44,6 +44,7 @@
 #include "front_syr2k.hip"
 #include "front_symm.hip"
 #include "front_lowrank.hip"
+#include "front_lanczos.hip"
 
 using namespace smcp;
 
@@ -2982,6 +2983,7 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 }  // extern "C"
 
 #include "lowrank.hip"
+#include "lanczos.hip"
 #include "kkt.hip"
 #include "kkt_many.hip"
 #include "kkt_res_many.hip"
