@@ -34,8 +34,8 @@ typedef struct csp_ctx csp_ctx;
                              CSP_TUNE_VERIFY_CACHE -- a cached quantity is older than the matrix it was derived from */
 #define SMCP_ETIMEOUT (-6) /* a workgroup of the one-launch blocked Cholesky (csrc/front_flow.hip) waited longer than 3 s for a tile
                              of another workgroup: the launch gave up instead of hanging (never seen; the results are invalid) */
-#define SMCP_ENOCONV (-7) /* the Jacobi iteration of csp_clique_eigvalsh did not converge on some clique within 30 sweeps, or the
-                             clique block holds a non-finite entry */
+#define SMCP_ENOCONV (-7) /* the Jacobi iteration of csp_clique_eigvalsh / csp_clique_eigh / csp_clique_project did not converge
+                             on some clique within 30 sweeps, or the clique block holds a non-finite entry */
 
 /* ---- symbolic layer (host only, no GPU needed) ------------------------------------- */
 
@@ -81,7 +81,8 @@ enum {
                              more pivots above the threshold than the r columns left room for (0 when r came from
                              csp_mrcompletion_rank with the same X and tol, up to rounding) */
   CSP_Q_EDM_CLAMPED = 19, /* 1 value: the same for the last csp_edmcompletion (r from csp_edmcompletion_rank) */
-  CSP_Q_CEIG_SWEEPS = 20  /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh on this context */
+  CSP_Q_CEIG_SWEEPS = 20  /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh, csp_clique_eigh or
+                             csp_clique_project on this context */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -255,6 +256,42 @@ int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd
  * SMCP_EINVAL for a null a or w, a replicated context, or w / ext overlapping a, b or each other.  The most sweeps of a
  * clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back; w and ext are not). */
 int csp_clique_eigvalsh(csp_ctx* ctx, const double* a, const double* b, double* w, double* ext, void* stream);
+/* Packed clique blocks: qptr[nsn] doubles in which clique k holds an nf_k x nf_k column-major block at
+ * [qptr[k], qptr[k + 1]), nf_k = nn_k + na_k, rows and columns in the order of the clique's rowidx (the supernode's own
+ * columns, then its separator rows).  Writes the nsn + 1 offsets to qptr_host (host).  Host only: no device is needed.
+ * SMCP_EINVAL for a null argument. */
+int csp_clique_ptr(csp_ctx* ctx, int64_t* qptr_host);
+/* Z (device, packed clique blocks) = the full symmetric block X_gg of every clique g of the blkval x, which is read as
+ * csp_clique_eigvalsh reads it and not written: the top-down gathers of the separator blocks, then one launch over all
+ * cliques.  SMCP_EINVAL for a null x or Z, a replicated context, or Z overlapping x.  Does not synchronise. */
+int csp_clique_gather(csp_ctx* ctx, const double* x, double* Z, void* stream);
+/* x (blkval) = P_V(sum_k E_k Z_k E_k^T) for packed clique blocks Z (device, not written), E_k the columns of the identity
+ * of clique k: every entry of V is the sum of that entry over the cliques that hold it.  Only the lower triangle of each Z_k
+ * is read.  Every slot of x is written; the slots above the diagonal of a supernode's diagonal block get zeros (the contract
+ * of csp_syr2k).  One launch per level, leaves first: a clique's own block, then its children's contributions in the order
+ * of its child list, no atomics: the same input gives the same bits.  SMCP_EINVAL for a null x or Z, a replicated or
+ * partitioned context, or x overlapping Z.  Does not synchronise. */
+int csp_clique_scatter(csp_ctx* ctx, const double* Z, double* x, void* stream);
+/* Eigenvectors of the clique blocks: w and ext as csp_clique_eigvalsh gives them in standard form (the same bits); Q
+ * (device, packed clique blocks): column j of block k is a unit eigenvector of A_gg for w[rowptr[k] + j].  The Jacobi
+ * iteration of csp_clique_eigvalsh with the rotations accumulated, in the slot of its pencil form; signs and the basis
+ * inside a degenerate eigenspace are unspecified but repeatable: the same input gives the same bits.  A clique wider
+ * than 89 rows runs from a slot in device memory on one workgroup and is slow.  Returns 0, SMCP_ENOCONV when a clique did
+ * not converge in 30 sweeps (a non-finite entry ends this way; w and Q of that clique are NaN, the others correct),
+ * SMCP_EINVAL for a null a, w or Q, a replicated context, or w / Q / ext overlapping a or each other.  The most sweeps of
+ * a clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back). */
+int csp_clique_eigh(csp_ctx* ctx, const double* a, double* w, double* Q, double* ext, void* stream);
+/* Clique-wise spectral projection: Z (device, packed clique blocks), block k = A_gg with its eigenvalues clipped to
+ * [lo, hi], formed as A_gg + sum over the eigenvalues w_j outside [lo, hi], ascending, of (clip(w_j) - w_j) q_j q_j^T: a
+ * block whose spectrum lies inside [lo, hi] is A_gg bit for bit (what csp_clique_gather gives), every block is exactly
+ * symmetric, and the work grows with the number of eigenvalues clipped.  This projects every block on its own; it is NOT
+ * the projection of A onto the cone of PSD-completable matrices, and the blocks of Z disagree where cliques overlap.
+ * w (device, rowptr[nsn] doubles, may be NULL) receives the eigenvalues of A_gg as csp_clique_eigh gives them; info
+ * (device, 2 nsn doubles): per clique the number of eigenvalues changed and sum_j (clip(w_j) - w_j)^2, which is
+ * |Z_k - A_gg|_F^2 in exact arithmetic.  lo = -inf and hi = +inf are allowed.  Returns 0, SMCP_ENOCONV as csp_clique_eigh
+ * (w, Z and info of that clique are NaN), SMCP_EINVAL unless lo <= hi (a NaN bound included), for a null a, Z or info, a
+ * replicated context, or Z / w / info overlapping a or each other.  Synchronises the stream. */
+int csp_clique_project(csp_ctx* ctx, const double* a, double lo, double hi, double* Z, double* w, double* info, void* stream);
 /* Lanczos on the dual cone: the extreme Ritz values of L^-1 D L^-T (D a blkval read as csp_symm reads it; -1 / theta_min is
  * the step at which L L^T + alpha D stops being positive definite) or, with D NULL, of L^-T L^-1 (1 / theta_max is the
  * smallest eigenvalue of L L^T), with full reorthogonalisation (classical Gram-Schmidt twice) and no host round trip per step.

@@ -5,6 +5,7 @@ not positive definite / not PD-completable, exactly as the reference's callers e
 (solvers.py:623-630,638-645).  All arithmetic happens in HIP kernels; there is no CPU path.
 """
 import ctypes
+import math
 
 import torch
 
@@ -219,7 +220,8 @@ def clique_extremes(A, B=None):
 
 
 def clique_eig_sweeps(symb):
-    """The most Jacobi sweeps any clique took in the last ``clique_eigvalsh`` on symb (CSP_Q_CEIG_SWEEPS)."""
+    """The most Jacobi sweeps any clique took in the last ``clique_eigvalsh``, ``clique_eigh`` or ``clique_project`` on symb
+    (CSP_Q_CEIG_SWEEPS)."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 20, ctypes.byref(out))
     return out.value
@@ -244,6 +246,119 @@ def max_step(X, D, return_clique=False):
     mu = float(e[0])
     alpha = -1.0 / mu if mu < 0.0 else math.inf
     return (alpha, int(e[1])) if return_clique else alpha
+
+
+def clique_ptr(symb):
+    """The offsets of the packed clique blocks: a numpy int64 array qptr of length Nsn + 1.  A packed block tensor is a
+    float64 device tensor of length qptr[-1] in which clique k holds an nf x nf column-major block at
+    [qptr[k], qptr[k + 1]), nf = nn + na, rows and columns in the order of the clique's rows in symb.rowidx: the
+    supernode's own columns, then its separator rows (csp_clique_ptr; host only, made once per Symbolic)."""
+    if "clique_ptr" not in symb._cache:
+        import numpy as np
+        q = np.zeros(symb.Nsn + 1, dtype=np.int64)
+        _chk(_lib.lib().csp_clique_ptr(symb.handle, q.ctypes.data), "clique_ptr")
+        symb._cache["clique_ptr"] = q
+    return symb._cache["clique_ptr"]
+
+
+def clique_block(symb, Z, k):
+    """The (nf, nf) view of block k of the packed block tensor Z, indexed [row, column] (no copy)."""
+    q = clique_ptr(symb)
+    _packed(symb, Z, "clique_block")
+    nf = int(symb.rowptr[k + 1] - symb.rowptr[k])
+    return Z[int(q[k]):int(q[k + 1])].view(nf, nf).t()
+
+
+def _packed(symb, Z, what):
+    """refuses what is not a packed block tensor of symb"""
+    if not (torch.is_tensor(Z) and Z.dtype == torch.float64 and Z.dim() == 1 and Z.is_contiguous()
+            and Z.shape[0] == int(clique_ptr(symb)[-1])):
+        raise ValueError("%s: Z is not a contiguous float64 tensor of length clique_ptr(symb)[-1]" % what)
+    return Z
+
+
+def clique_gather(X):
+    """The clique blocks of the cspmatrix X as a packed block tensor (``clique_ptr``): block k is the full symmetric
+    X_gg of clique k = g (of a supernode's diagonal block the lower triangle counts).  X is not written.  One launch
+    over all cliques behind the top-down gathers of the separator blocks (csp_clique_gather)."""
+    symb = X.symb
+    _ensure(symb)
+    Z = torch.empty(int(clique_ptr(symb)[-1]), dtype=torch.float64, device=X.blkval.device)
+    _chk(_lib.lib().csp_clique_gather(symb.handle, X.blkval.data_ptr(), Z.data_ptr(), _stream()), "clique_gather")
+    return Z
+
+
+def clique_scatter(symb, Z, reduce="sum"):
+    """The cspmatrix P_V(sum_k E_k Z_k E_k^T) of the packed block tensor Z: every entry of the pattern is the sum
+    (reduce="sum") or the mean (reduce="mean": the sum divided by ``clique_multiplicity``) of that entry over the cliques
+    that hold it.  Only the lower triangle of each block is read; Z is not written.  The slots above the diagonal of a
+    supernode's diagonal block are zero, as ``syr2k`` leaves them.  One launch per level of the clique tree, leaves first,
+    every sum in a fixed order: the same input gives the same bits (csp_clique_scatter).  ValueError for another
+    `reduce` or a tensor that is not a packed block tensor of symb."""
+    if reduce not in ("sum", "mean"):
+        raise ValueError("clique_scatter: reduce must be 'sum' or 'mean'")
+    _ensure(symb)
+    if not _packed(symb, Z, "clique_scatter").is_cuda:
+        raise ValueError("clique_scatter: Z is not a device tensor")
+    X = cspmatrix(symb, torch.empty(symb.blklen, dtype=torch.float64, device=Z.device))
+    _chk(_lib.lib().csp_clique_scatter(symb.handle, Z.data_ptr(), X.blkval.data_ptr(), _stream()), "clique_scatter")
+    if reduce == "mean":
+        X.blkval /= clique_multiplicity(symb).to(Z.device)
+    return X
+
+
+def clique_multiplicity(symb):
+    """Per slot of blkval the number of cliques that hold the entry, a float64 device tensor: the scatter of all-ones
+    blocks, made once per Symbolic; 1 on the unused slots above the diagonal of a supernode's diagonal block."""
+    if "clique_mult" not in symb._cache:
+        _ensure(symb)
+        ones = torch.ones(int(clique_ptr(symb)[-1]), dtype=torch.float64, device="cuda:%d" % symb._device)
+        symb._cache["clique_mult"] = clique_scatter(symb, ones).blkval.clamp_(min=1.0)
+    return symb._cache["clique_mult"]
+
+
+def clique_eigh(A):
+    """(w, Q): w as ``clique_eigvalsh(A)`` gives it (the same bits), Q a packed block tensor (``clique_ptr``) whose block
+    k has as column j a unit eigenvector of A_gg for w[rowptr[k] + j]; ``clique_block(symb, Q, k)`` is that matrix.
+    Signs and the basis inside a degenerate eigenspace are unspecified, but the same input gives the same bits.  A is
+    not written.  RuntimeError when a clique did not converge in 30 Jacobi sweeps (a non-finite entry ends this way).
+    A clique wider than 89 rows does not fit the on-chip memory of its workgroup and is slow: one workgroup works on it
+    from device memory (csp_clique_eigh)."""
+    symb = A.symb
+    _ensure(symb)
+    dev = A.blkval.device
+    w = torch.empty(int(symb.rowptr[-1]), dtype=torch.float64, device=dev)
+    Q = torch.empty(int(clique_ptr(symb)[-1]), dtype=torch.float64, device=dev)
+    _chk(_lib.lib().csp_clique_eigh(symb.handle, A.blkval.data_ptr(), w.data_ptr(), Q.data_ptr(), None, _stream()), "clique_eigh")
+    return w, Q
+
+
+def clique_project(X, lo=0.0, hi=math.inf, return_info=False):
+    """Z, a packed block tensor (``clique_ptr``): block k is X_gg with its eigenvalues clipped to [lo, hi], the nearest
+    matrix to X_gg in the Frobenius norm with lo I <= Z_k <= hi I.  With return_info=True: (Z, w, info), w the
+    eigenvalues of the blocks of X as ``clique_eigh`` gives them and info an (Nsn, 2) float64 device tensor, per clique
+    the number of eigenvalues changed and sum_j (clip(w_j) - w_j)^2 = |Z_k - X_gg|_F^2.
+    This projects every clique block on its own.  It is NOT the Frobenius projection of X onto the cone C_V of
+    PSD-completable matrices: it is the building block of the methods that compute it or solve over it (clique-splitting
+    ADMM, Dykstra's alternating projections).  The blocks of Z disagree on the separators until they are averaged
+    (``clique_scatter(symb, Z, "mean")``).
+    A block whose spectrum lies inside [lo, hi] comes back as the bits of ``clique_gather(X)``; every block is exactly
+    symmetric; the work grows with the number of eigenvalues clipped.  Wide cliques are slow: beyond 89 rows one workgroup
+    works on the block from device memory.  X is not written; lo = -inf and hi = inf are allowed.  ValueError unless
+    lo <= hi (a NaN bound included), RuntimeError when a clique did not converge in 30 Jacobi sweeps (a non-finite entry
+    ends this way; csp_clique_project)."""
+    lo, hi = float(lo), float(hi)
+    if not lo <= hi:
+        raise ValueError("clique_project: needs lo <= hi (got %r, %r)" % (lo, hi))
+    symb = X.symb
+    _ensure(symb)
+    dev = X.blkval.device
+    Z = torch.empty(int(clique_ptr(symb)[-1]), dtype=torch.float64, device=dev)
+    w = torch.empty(int(symb.rowptr[-1]), dtype=torch.float64, device=dev) if return_info else None
+    info = torch.empty((symb.Nsn, 2), dtype=torch.float64, device=dev)
+    _chk(_lib.lib().csp_clique_project(symb.handle, X.blkval.data_ptr(), lo, hi, Z.data_ptr(), None if w is None else w.data_ptr(),
+                                       info.data_ptr(), _stream()), "clique_project")
+    return (Z, w, info) if return_info else Z
 
 
 LANCZOS_JMAX = 128    # csrc/front_lanczos.hip: LZ_JMAX

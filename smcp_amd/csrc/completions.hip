@@ -210,6 +210,66 @@ int psd_setup(csp_ctx* c) {
   return dev_upload(&P.ulist, ulist, D.mem);      // last: ulist marks the plan as built
 }
 
+// ---- packed clique blocks (front_ceig.hip) --------------------------------------------------------------------------
+// block k (nf x nf, column-major, rows and columns in the order of the clique's rowidx) lies at [q[k], q[k + 1])
+std::vector<int64_t> clique_ptr_of(const Symbolic& S) {
+  std::vector<int64_t> q(S.nsn + 1, 0);
+  for (int64_t k = 0; k < S.nsn; ++k) q[k + 1] = q[k] + S.nf(k) * S.nf(k);
+  return q;
+}
+// the device copy of these offsets, made by the first call that needs it
+int qptr_setup(csp_ctx* c) {
+  if (c->D.mrc.qptr) return 0;
+  const std::vector<int64_t> q = clique_ptr_of(c->S);
+  c->qlen = q.back();
+  return dev_upload(&c->D.mrc.qptr, q, c->D.mem);
+}
+
+// some output range overlaps an input range or another output range (a null range overlaps nothing)
+using DRange = std::pair<const double*, int64_t>;
+bool ranges_overlap(std::initializer_list<DRange> outs, std::initializer_list<DRange> ins) {
+  auto overlap = [](const DRange& p, const DRange& q) { return p.first && q.first && p.first < q.first + q.second && q.first < p.first + p.second; };
+  for (const DRange* o = outs.begin(); o != outs.end(); ++o) {
+    for (const DRange& i : ins) if (overlap(*o, i)) return true;
+    for (const DRange* o2 = o + 1; o2 != outs.end(); ++o2) if (overlap(*o, *o2)) return true;
+  }
+  return false;
+}
+
+// csp_clique_eigh (vmode 0) and csp_clique_project (vmode 1): the launches of csp_clique_eigvalsh in standard form with
+// k_ceig_vec in the slots of the pencil form, under the same kernel ids; ext null: the context's own four doubles
+int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, double* Q, double* w, double* ext, double* info,
+                  hipStream_t st) {
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  const int64_t nsn = S.nsn;
+  if (int rc = mrc_setup(c)) return rc;
+  if (!ext && !D.mrc.ext)
+    if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
+  std::vector<int64_t> need, ranges;
+  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return ceig_slot2(S.nf(k)); }, need, ranges, st)) return rc;
+  gather_all(c, a, 0, 1, D.upd, st);
+  MrcArgs m = mrc_args(c, a, 0.0);
+  m.w = w;
+  m.Q = Q;
+  m.qptr = D.mrc.qptr;
+  m.lo = lo;
+  m.hi = hi;
+  m.pinfo = info;
+  m.vmode = vmode;
+  if (int rc = mrc_launch<k_ceig_vec>(c, KID_ceig, m, need, 0, nsn, st)) return rc;
+  int32_t* dout = D.mrc.ints + 2 * nsn;
+  launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
+         (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);
+  HIPCHK(end_call(c));
+  int32_t out[3];
+  HIPCHK(hipMemcpyAsync(out, dout, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  c->ceig_sweeps = out[2];
+  if (out[1]) return SMCP_ENOCONV;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,6 +341,71 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   if (out[0]) return out[0];
   if (out[1]) return SMCP_ENOCONV;
   return 0;
+}
+
+// ---- packed clique blocks: gather, scatter, eigenvectors, projection (front_ceig.hip) -------------------------------
+int csp_clique_ptr(csp_ctx* c, int64_t* qptr_host) {
+  if (!c || !qptr_host) return SMCP_EINVAL;
+  const std::vector<int64_t> q = clique_ptr_of(c->S);
+  std::copy(q.begin(), q.end(), qptr_host);
+  return 0;
+}
+
+// One launch over all cliques behind the top-down gathers of the separator blocks.
+int csp_clique_gather(csp_ctx* c, const double* x, double* Z, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !Z || c->ntrial != 1) return SMCP_EINVAL;
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  if (int rc = qptr_setup(c)) return rc;
+  if (ranges_overlap({{Z, c->qlen}}, {{x, S.blklen()}})) return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  gather_all(c, x, 0, 1, D.upd, st);
+  const unsigned parts = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, S.max_front * S.max_front / (MRC_NT * 32)));
+  launch(c, KID_gather_level, k_clique_gather, dim3((unsigned)S.nsn, parts), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, x, (const double*)D.upd,
+         (const int64_t*)D.mrc.qptr, Z);
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// One launch per level, leaves first; D.upd is the update stack, as in csp_cholesky.
+int csp_clique_scatter(csp_ctx* c, const double* Z, double* x, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!x || !Z || c->ntrial != 1 || c->xr_world > 1) return SMCP_EINVAL;
+  if (int rc = qptr_setup(c)) return rc;
+  if (ranges_overlap({{x, c->S.blklen()}}, {{Z, c->qlen}})) return SMCP_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  invalidate_tags(c, x);
+  TreeArgs a = tree_args(c);
+  for_levels_up(c, [&](const int32_t* lev, int cnt) {
+    a.lev = lev;
+    launch(c, KID_gather_level, k_clique_scatter, dim3((unsigned)cnt), dim3(MRC_NT), st, a, Z, (const int64_t*)c->D.mrc.qptr, x);
+  });
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+int csp_clique_eigh(csp_ctx* c, const double* a, double* w, double* Q, double* ext, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!a || !w || !Q || c->ntrial != 1) return SMCP_EINVAL;
+  if (int rc = qptr_setup(c)) return rc;
+  const int64_t wlen = c->S.rowptr[c->S.nsn];
+  if (ranges_overlap({{w, wlen}, {Q, c->qlen}, {ext, 4}}, {{a, c->S.blklen()}})) return SMCP_EINVAL;
+  return ceig_vec_pass(c, a, 0, 0.0, 0.0, Q, w, ext, nullptr, (hipStream_t)stream);
+}
+
+int csp_clique_project(csp_ctx* c, const double* a, double lo, double hi, double* Z, double* w, double* info, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!a || !Z || !info || !(lo <= hi) || c->ntrial != 1) return SMCP_EINVAL;
+  if (int rc = qptr_setup(c)) return rc;
+  const int64_t wlen = c->S.rowptr[c->S.nsn];
+  if (ranges_overlap({{Z, c->qlen}, {w, wlen}, {info, 2 * c->S.nsn}}, {{a, c->S.blklen()}})) return SMCP_EINVAL;
+  if (!w) {
+    if (!c->D.mrc.wbuf)
+      if (int rc = dev_alloc(&c->D.mrc.wbuf, wlen, c->D.mem)) return rc;
+    w = c->D.mrc.wbuf;
+  }
+  return ceig_vec_pass(c, a, 1, lo, hi, Z, w, nullptr, info, (hipStream_t)stream);
 }
 
 // ---- Euclidean distance matrix completion (front_edm.hip) -----------------------------------------------------------

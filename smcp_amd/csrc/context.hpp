@@ -71,11 +71,14 @@ struct SymmPlan {
 // slots of the cliques too wide for LDS (ws, cap doubles), per clique rank and flag (2 nsn) + the reduced results (ints),
 // diag(X), and the cliques of every launch (list, sorted by slot size within a launch); for the clique spectra
 // (front_ceig.hip) the gathered separator blocks of the second matrix of a pencil (upd2, updlen doubles, made by the first
-// pencil call) and the four extremes of a call that passes no buffer for them (ext)
+// pencil call) and the four extremes of a call that passes no buffer for them (ext); for the packed clique blocks the
+// offsets of the blocks (qptr, nsn + 1, made by the first call that takes or gives such blocks) and the eigenvalues of a
+// csp_clique_project that passes no buffer for them (wbuf, rowptr[nsn] doubles)
 struct CompletionWs {
   double* ws = nullptr; int64_t cap = 0;
   int32_t* ints = nullptr; double* xdiag = nullptr; int32_t* list = nullptr;
   double* upd2 = nullptr; double* ext = nullptr;
+  int64_t* qptr = nullptr; double* wbuf = nullptr;
 };
 
 // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
@@ -353,7 +356,8 @@ struct csp_ctx : smcp::PartitionTables {
   std::vector<uint8_t> large_mask;   // per clique: a large (HBM-class) front
   int64_t mrc_clamped = 0;              // cliques of the last csp_mrcompletion whose Schur factor lost columns to the r-column cap
   int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
-  int64_t ceig_sweeps = 0;              // the most Jacobi sweeps a clique took in the last csp_clique_eigvalsh
+  int64_t ceig_sweeps = 0;              // the most Jacobi sweeps a clique took in the last csp_clique_eigvalsh / _eigh / _project
+  int64_t qlen = 0;                     // doubles of the packed clique blocks (set with D.mrc.qptr)
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
   std::vector<PsdLevel> psd_lev;        // per level with fill work, root first
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy

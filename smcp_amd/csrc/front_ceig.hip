@@ -16,6 +16,18 @@
 // No eigenvectors are accumulated.  Every entry of a step is one expression of entries of the step before and every
 // reduction is a fixed tree: the same input gives the same bits.
 // k_ceig_reduce: the smallest and largest eigenvalue over all cliques with the lowest clique attaining each, and the status.
+//
+// With eigenvectors (csp_clique_eigh, csp_clique_project): k_ceig_vec, the standard form of k_ceig in the slot of the pencil
+// form with V where that keeps G.  V starts as I; every Jacobi step rotates columns p, q of V by the step's (s, tau) tables in
+// one more pass shaped as the column pass on F (ceig_jacobi<true>: the arithmetic on F is that of k_ceig, so are the bits of
+// w).  The rank sort of the diagonal sends column i of V to column rank(i) of block k of Q (vmode 0).  vmode 1, the
+// projection of the block on {lo I <= Z <= hi I}: the sorted spectrum stays in the slot, A_gg is formed again over F, and
+// Z = A_gg + sum over the eigenvalues outside [lo, hi], ascending, of (clip(w_j) - w_j) q_j q_j^T, one thread per entry of the
+// lower triangle, mirrored on store: a block whose spectrum lies inside [lo, hi] comes back as the bits of A_gg, and the work
+// grows with the number of eigenvalues clipped.
+// k_clique_gather / k_clique_scatter: the packed clique blocks (block k: nf x nf, column-major, at qptr[k]) from a blkval
+// with its separator blocks gathered, and back: x = P_V(sum_k E_k Z_k E_k^T), one launch per level, leaves first, a clique's
+// panel and update block from the lower triangle of Z_k, then its children's update blocks by add_children (front_generic.hip).
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -62,7 +74,9 @@ __device__ inline void ceig_pair(int m, int r, int t, int& p, int& q) {
 // The cyclic Jacobi of the symmetric nf x nf matrix F (full storage, column-major, overwritten; its diagonal ends as the
 // eigenvalues).  tab: 5 * ((nf + 1) / 2) doubles.  Returns the sweeps taken; *noconv = 1 when F holds a non-finite entry or
 // CEIG_MAX_SWEEPS did not reach the stopping rule.
-__device__ inline int ceig_jacobi(int nf, double* F, double* tab, double* red, int* noconv) {
+// VEC: V (nf x nf, the identity on entry) <- V J for every rotation J: its columns end as the eigenvectors, column i for F_ii.
+template <bool VEC = false>
+__device__ inline int ceig_jacobi(int nf, double* F, double* tab, double* red, int* noconv, double* V = nullptr) {
   const int m = nf + (nf & 1), h = m / 2, steps = m - 1;
   double* tc = tab;            // per pair of the step: s (0: skipped), tau = s / (1 + c), the new a_pp, the new a_qq, (p, q)
   double* tt = tab + h;
@@ -143,16 +157,32 @@ __device__ inline int ceig_jacobi(int nf, double* F, double* tab, double* red, i
         i += cdi; t += cdt;
         if (i >= nf) { i -= nf; ++t; }
       }
+      if constexpr (VEC) {
+        for (int i = ci0, t = ct0; t < h;) {                      // columns p, q of V: V <- V J (nothing of F is read or written)
+          const double s = tc[t];
+          if (s != 0.0) {
+            const double tau = tt[t];
+            double* Vp = V + i + (int64_t)pq[2 * t] * nf;
+            double* Vq = V + i + (int64_t)pq[2 * t + 1] * nf;
+            const double g = *Vp, hh = *Vq;
+            *Vp = g - s * (hh + g * tau);
+            *Vq = hh + s * (g - hh * tau);
+          }
+          i += cdi; t += cdt;
+          if (i >= nf) { i -= nf; ++t; }
+        }
+      }
       __syncthreads();
     }
   }
   return sweeps;
 }
 
-// the full symmetric block of clique d of the matrix with panel P (nf x nn) and gathered separator block U (na x na)
-__device__ inline void ceig_form(const CliqueDesc& d, const double* P, const double* U, double* F) {
+// the full symmetric block of clique d of the matrix with panel P (nf x nn) and gathered separator block U (na x na);
+// workgroup `part` of `nparts` that share the block
+__device__ inline void ceig_form(const CliqueDesc& d, const double* P, const double* U, double* F, int part = 0, int nparts = 1) {
   const int nn = d.nn, na = d.na, nf = nn + na;
-  for (int e = SMCP_TID; e < nf * nf; e += MRC_NT) {
+  for (int e = part * MRC_NT + SMCP_TID; e < nf * nf; e += nparts * MRC_NT) {
     const int i = e % nf, j = e / nf;
     if (i >= j) {
       const double v = j < nn ? P[i + (int64_t)j * nf] : U[(i - nn) + (int64_t)(j - nn) * na];
@@ -221,6 +251,117 @@ __global__ void __launch_bounds__(MRC_NT) k_ceig(MrcArgs a) {
     }
     __syncthreads();
   }
+}
+
+// MrcArgs: as k_ceig in standard form; Q, qptr, lo, hi, pinfo, vmode: see there.  A clique that did not converge leaves NaN
+// in its w, its block of Q and (vmode 1) its two entries of pinfo.
+__global__ void __launch_bounds__(MRC_NT) k_ceig_vec(MrcArgs a) {
+  extern __shared__ double mrc_lds[];
+  __shared__ double red[MRC_NT];
+  __shared__ double stab[5 * CEIG_TAB_H];      // as in k_ceig
+  double* ws = a.ws ? a.ws + (int64_t)blockIdx.x * a.slot : mrc_lds;
+  for (int e = blockIdx.x; e < a.cnt; e += gridDim.x) {
+    const int k = a.lev[e];
+    const CliqueDesc d = a.cl[k];
+    const int nf = d.nn + d.na;
+    double* F = ws;
+    double* V = F + (int64_t)nf * nf;
+    double* tab = V + (int64_t)nf * nf;
+    double* dg = tab;                          // the diagonal; behind it the rank of every column and the column of every
+    int* rk = (int*)(tab + nf);                // rank (2 nf ints), then the sorted spectrum
+    int* col = rk + nf;
+    double* sw = tab + 2 * nf;
+    double* w = a.w + d.rows;
+    double* Zk = a.Q + a.qptr[k];
+    ceig_form(d, a.x + d.blk, a.upd + d.upd, F);
+    for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) V[t] = (t % (nf + 1) == 0) ? 1.0 : 0.0;
+    __syncthreads();
+    int noconv;
+    const int sweeps = ceig_jacobi<true>(nf, F, (nf + 1) / 2 <= CEIG_TAB_H ? stab : tab, red, &noconv, V);
+    if (!noconv) {
+      for (int i = SMCP_TID; i < nf; i += MRC_NT) dg[i] = F[i + (int64_t)i * nf];
+      __syncthreads();
+      for (int i = SMCP_TID; i < nf; i += MRC_NT) {
+        const double v = dg[i];
+        int r = 0;
+        for (int j = 0; j < nf; ++j) r += (dg[j] < v || (dg[j] == v && j < i)) ? 1 : 0;
+        w[r] = v;
+        sw[r] = v;
+        rk[i] = r;
+        col[r] = i;
+      }
+      __syncthreads();
+      if (a.vmode == 0) {
+        for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) Zk[t % nf + (int64_t)rk[t / nf] * nf] = V[t];
+      } else {
+        ceig_form(d, a.x + d.blk, a.upd + d.upd, F);
+        const double lo = a.lo, hi = a.hi;
+        double cl = 0.0, ch = 0.0, sq = 0.0;
+        for (int r = SMCP_TID; r < nf; r += MRC_NT) {
+          const double v = sw[r];
+          if (v < lo) { cl += 1.0; sq += (lo - v) * (lo - v); }
+          else if (v > hi) { ch += 1.0; sq += (hi - v) * (hi - v); }
+        }
+        const int nlo = (int)ceig_reduce(cl, false, red), nhi = (int)ceig_reduce(ch, false, red);
+        sq = ceig_reduce(sq, false, red);
+        for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) {
+          const int i = t % nf, j = t / nf;
+          if (i >= j) {
+            double z = F[t];
+            for (int r = 0; r < nlo; ++r) {
+              const double* q = V + (int64_t)col[r] * nf;
+              z += (lo - sw[r]) * (q[i] * q[j]);
+            }
+            for (int r = nf - nhi; r < nf; ++r) {
+              const double* q = V + (int64_t)col[r] * nf;
+              z += (hi - sw[r]) * (q[i] * q[j]);
+            }
+            Zk[i + (int64_t)j * nf] = z;
+            Zk[j + (int64_t)i * nf] = z;
+          }
+        }
+        if (SMCP_TID == 0) {
+          a.pinfo[2 * k] = (double)(nlo + nhi);
+          a.pinfo[2 * k + 1] = sq;
+        }
+      }
+    } else {
+      for (int i = SMCP_TID; i < nf; i += MRC_NT) w[i] = NAN;
+      for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) Zk[t] = NAN;
+      if (a.vmode && SMCP_TID == 0) a.pinfo[2 * k] = a.pinfo[2 * k + 1] = NAN;
+    }
+    if (SMCP_TID == 0) {
+      a.rank[k] = sweeps;
+      a.flag[k] = noconv ? CEIG_NO_CONV : 0;
+    }
+    __syncthreads();
+  }
+}
+
+// Z_k = the full symmetric block of clique k = blockIdx.x of the matrix with blkval x and gathered separator blocks upd:
+// ceig_form straight to global memory, gridDim.y workgroups per clique
+__global__ void __launch_bounds__(MRC_NT) k_clique_gather(const CliqueDesc* cl, const double* x, const double* upd, const int64_t* qptr,
+                                                           double* Z) {
+  const CliqueDesc d = cl[blockIdx.x];
+  ceig_form(d, x + d.blk, upd + d.upd, Z + qptr[blockIdx.x], blockIdx.y, gridDim.y);
+}
+
+// One level of x = P_V(sum_k E_k Z_k E_k^T), a workgroup per clique: the panel (zeros above the diagonal of the diagonal
+// block) and the update block from the lower triangle of Z_k, then the children's update blocks on top in the order of chidx
+__global__ void __launch_bounds__(MRC_NT) k_clique_scatter(TreeArgs a, const double* Z, const int64_t* qptr, double* x) {
+  const int k = a.lev[blockIdx.x];
+  const CliqueDesc d = a.cl[k];
+  const int nn = d.nn, na = d.na, nf = nn + na;
+  const double* Zk = Z + qptr[k];
+  double* P = x + d.blk;
+  double* Uk = a.upd + d.upd;
+  for (int e = SMCP_TID; e < nf * nn; e += MRC_NT) P[e] = e % nf >= e / nf ? Zk[e] : 0.0;
+  for (int e = SMCP_TID; e < na * na; e += MRC_NT) {
+    const int i = e % na, j = e / na;
+    Uk[e] = i >= j ? Zk[(nn + i) + (int64_t)(nn + j) * nf] : 0.0;
+  }
+  __syncthreads();
+  add_children(a, d, a.upd, P, Uk, 1.0, 1.0);
 }
 
 // ext[0] = the smallest eigenvalue over all cliques, ext[1] = the lowest clique attaining it, ext[2] = the largest,

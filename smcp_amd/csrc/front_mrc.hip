@@ -49,6 +49,11 @@ struct MrcArgs {
   const double* x2;         // k_ceig (front_ceig.hip): blkval of B and B_AA of every clique (null: standard form), the
   const double* upd2;       // eigenvalues of clique k at w + cl[k].rows
   double* w;
+  double* Q;                // k_ceig_vec: the packed clique blocks it writes (block k at Q + qptr[k]): the eigenvectors
+  const int64_t* qptr;      // (vmode 0) or the block with its spectrum clipped to [lo, hi] (vmode 1), then per clique the
+  double lo, hi;            // eigenvalues changed and the squared distance at pinfo + 2 k
+  double* pinfo;
+  int vmode;
 };
 
 // (value, index) of the largest val(i), i < n; ties go to the lowest index, -1 when every value is -inf / NaN.  The
