@@ -292,6 +292,29 @@ int csp_clique_eigh(csp_ctx* ctx, const double* a, double* w, double* Q, double*
  * (w, Z and info of that clique are NaN), SMCP_EINVAL unless lo <= hi (a NaN bound included), for a null a, Z or info, a
  * replicated context, or Z / w / info overlapping a or each other.  Synchronises the stream. */
 int csp_clique_project(csp_ctx* ctx, const double* a, double lo, double hi, double* Z, double* w, double* info, void* stream);
+/* The Frobenius projection of the blkval a (read as csp_clique_eigvalsh reads it, never written) onto the cone K of matrices
+ * on the pattern whose clique blocks are all positive semidefinite, in the norm of csp_dot: iterations it0 .. it0 + nsteps - 1
+ * of a clique-splitting ADMM with penalty rho and over-relaxation relax on a state the caller owns, in place: x (blkval),
+ * U and W (device, packed clique blocks: U_k the scaled dual of clique k, negative semidefinite; W_k = Z_k - U_k with Z_k the
+ * clique's positive semidefinite copy).  The caller starts with x = a, U = 0 (or the U of an earlier run with the same rho)
+ * and W = the clique blocks of a (csp_clique_gather) minus U.  One iteration, every clique on its own:
+ *   T_k = Z_k + relax (x_gg - Z_k) + U_k;  U_k <- the negative part of T_k;  Z_k <- T_k - U_k;  W_k <- T_k - 2 U_k,
+ * then x <- (a + rho sum_k E_k W_k E_k^T) / (1 + rho mult) entry by entry, mult = the cliques that hold the entry; the slots
+ * above the diagonal of a supernode's diagonal block become 0 whatever a holds there.  Row it of hist (device, 4 doubles per
+ * iteration, rows 0 .. it0 + nsteps - 1 must exist): sum_k |x_gg - Z_k|_F^2 with the x before the update, |x_new - x_old|^2
+ * in the norm of csp_dot, the negative eigenvalues of all T_k, and 1 + the lowest clique whose Jacobi iteration did not
+ * converge in 30 sweeps (0: none; a non-finite entry ends this way, and U_k, W_k and the sums are then NaN).  A block T_k
+ * without a negative eigenvalue leaves U_k exactly 0.  At the fixed point x is the projection and x - a = -rho sum_k E_k U_k E_k^T
+ * lies in the dual cone, the positive semidefinite matrices on the pattern.  Every sum in a fixed order, no atomics: the same
+ * input gives the same bits, and 1 + 2 steps in two calls are the 3 steps of one.  A clique wider than 89 rows runs on one
+ * workgroup from device memory, in every iteration.  Does not synchronise and reads nothing back (the first call on a context
+ * builds the workspace and may wait).  SMCP_EINVAL for a null pointer, any overlap among a, x, U, W and hist, rho <= 0, relax
+ * outside (0, 2), it0 < 0, nsteps < 1, a replicated or partitioned context.
+ * csp_cone_project_sweeps: *out (host) = the most Jacobi sweeps of a clique in any iteration since the call with it0 = 0;
+ * waits for the stream.  SMCP_EINVAL before the first csp_cone_project_steps on the context. */
+int csp_cone_project_steps(csp_ctx* ctx, const double* a, double* x, double* U, double* W, double rho, double relax, int64_t it0,
+                           int64_t nsteps, double* hist, void* stream);
+int csp_cone_project_sweeps(csp_ctx* ctx, int64_t* out, void* stream);
 /* Lanczos on the dual cone: the extreme Ritz values of L^-1 D L^-T (D a blkval read as csp_symm reads it; -1 / theta_min is
  * the step at which L L^T + alpha D stops being positive definite) or, with D NULL, of L^-T L^-1 (1 / theta_max is the
  * smallest eigenvalue of L L^T), with full reorthogonalisation (classical Gram-Schmidt twice) and no host round trip per step.

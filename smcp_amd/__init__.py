@@ -14,6 +14,7 @@ from .base import dual_max_step, dual_margin  # noqa: F401  (scipy matrices; the
 from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2k, syrk, syr2, symm, dot, logdiagsum, lowrank_factor, LowRankFactor  # noqa: F401
 from .chordal import clique_eigvalsh, clique_extremes  # noqa: F401
 from .chordal import clique_ptr, clique_block, clique_gather, clique_scatter, clique_multiplicity, clique_eigh, clique_project  # noqa: F401
+from .base import cone_project  # noqa: F401  (scipy matrices; the cspmatrix form is smcp_amd.chordal.cone_project)
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion
 
 __version__ = "0.1.0"

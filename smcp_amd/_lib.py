@@ -55,6 +55,8 @@ SIGNATURES = {
     "csp_clique_scatter": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "csp_clique_eigh": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "csp_clique_project": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
+    "csp_cone_project_steps": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_vp, c_vp]),
+    "csp_cone_project_sweeps": (ctypes.c_int, [c_vp, c_i64p, c_vp]),
     "csp_lanczos_work_len": (c_i64, [c_i64, c_i64]),
     "csp_lanczos_steps": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "csp_lanczos_ritz": (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp]),

@@ -552,6 +552,21 @@ def cone_margin(X):
     return chordal.cone_margin(_on_chordal_pattern([X], "cone_margin")[0])[0]
 
 
+def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, return_info=False):
+    """The nearest matrix to the sparse symmetric A (scipy sparse, either triangle or both) on its chordal pattern that has a
+    positive semidefinite completion (cone="primal") or is itself positive semidefinite (cone="dual"), in the Frobenius norm:
+    a symmetric scipy CSC matrix in the coordinates of A (smcp_amd.chordal.cone_project; read its docstring for what kind
+    of input the iteration is for).  return_info=True: (X, info) with the dict of that call, without the device tensors `hist`
+    and `U`.  ValueError for a pattern that is not chordal."""
+    from . import chordal
+    Ac = _on_chordal_pattern([A], "cone_project")[0]
+    out = chordal.cone_project(Ac, cone=cone, tol=tol, maxit=maxit, rho=rho, relax=relax, return_info=return_info)
+    if not return_info:
+        return out.spmatrix(reordered=False, symmetric=True)
+    info = {k: v for k, v in out[1].items() if k not in ("hist", "U")}
+    return out[0].spmatrix(reordered=False, symmetric=True), info
+
+
 def max_step(X, D):
     """sup{alpha >= 0 : X + alpha D has a positive definite completion} for sparse symmetric X, D (scipy sparse, either
     triangle or both) whose joint pattern is chordal and X inside the cone; math.inf when no step leaves it

@@ -27,17 +27,20 @@ int64_t lds_ceiling() {
 }
 
 // Runs Kern over the cliques list[b, e) (host copy; the device copy is D.mrc.list), which ascend in slot size need[]
-// (doubles): those whose slot fits in LDS one workgroup each, in launches by size class, the rest over HBM slots
+// (doubles): those whose slot fits in LDS one workgroup each, in launches by size class, the rest over HBM slots.
+// list: another device list than D.mrc.list (one that outlives the call)
 template <auto Kern>
-int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need, int64_t b, int64_t e, hipStream_t st) {
+int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need, int64_t b, int64_t e, hipStream_t st,
+               const int32_t* list = nullptr) {
   DeviceCtx& D = c->D;
+  if (!list) list = D.mrc.list;
   const int64_t lds_max = lds_ceiling<Kern>();
   int64_t q = b;
   for (int64_t cap : {(int64_t)8192, (int64_t)16384, (int64_t)32768, (int64_t)65536, MRC_LDS}) {
     int64_t q2 = q;
     while (q2 < e && need[q2] * (int64_t)sizeof(double) <= std::min(cap, lds_max)) ++q2;
     if (q2 > q) {
-      a.lev = D.mrc.list + q;
+      a.lev = list + q;
       a.cnt = (int)(q2 - q);
       a.ws = nullptr;
       launch_lds(c, kid, Kern, dim3((unsigned)(q2 - q)), dim3(MRC_NT), (size_t)need[q2 - 1] * sizeof(double), st, a);
@@ -48,7 +51,7 @@ int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need,
     const int64_t slot = (need[e - 1] + 31) / 32 * 32;
     const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
     if (int rc = dev_grow(&D.mrc.ws, &D.mrc.cap, G * slot, D.mem, st)) return rc;
-    a.lev = D.mrc.list + q;
+    a.lev = list + q;
     a.cnt = (int)(e - q);
     a.ws = D.mrc.ws;
     a.slot = slot;
@@ -270,6 +273,41 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
   return 0;
 }
 
+// workgroups of k_cone_update, which is also the number of its partial sums: a function of blklen alone
+int64_t cone_parts(const Symbolic& S) { return std::max<int64_t>(1, std::min<int64_t>(1024, (S.blklen() + 4 * MRC_NT - 1) / (4 * MRC_NT))); }
+
+// What csp_cone_project_steps keeps for the life of the context, made by its first call (with synchronous uploads):
+// the workspace of CompletionWs, the slot-sorted list of all cliques with its slot sizes (a list of its own: D.mrc.list
+// belongs to whichever call runs) and the signed multiplicities, by one launch of k_cone_mult per level, leaves first
+int cone_setup(csp_ctx* c, hipStream_t st) {
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  if (int rc = mrc_setup(c)) return rc;
+  if (int rc = qptr_setup(c)) return rc;
+  if (D.mrc.cone_mw) return 0;
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  for (int64_t k : S.levidx) tmp.push_back({ceig_slot2(S.nf(k)), (int32_t)k});
+  std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+  std::vector<int32_t> list;
+  c->cone_need.clear();
+  for (auto& t : tmp) { c->cone_need.push_back(t.first); list.push_back(t.second); }
+  if (int rc = dev_upload(&D.mrc.cone_list, list, D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.cone_sw, S.blklen(), D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.cone_info, 2 * S.nsn, D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.cone_part, cone_parts(S), D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.cone_sweeps, 1, D.mem)) return rc;
+  double* mw = nullptr;
+  if (int rc = dev_alloc(&mw, S.blklen(), D.mem)) return rc;
+  TreeArgs a = tree_args(c);
+  for_levels_up(c, [&](const int32_t* lev, int cnt) {
+    a.lev = lev;
+    launch(c, KID_gather_level, k_cone_mult, dim3((unsigned)cnt), dim3(MRC_NT), st, a, mw);
+  });
+  HIPCHK(hipMemsetAsync(D.mrc.cone_sweeps, 0, sizeof(int32_t), st));
+  D.mrc.cone_mw = mw;                    // last: marks the workspace as made
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -406,6 +444,60 @@ int csp_clique_project(csp_ctx* c, const double* a, double lo, double hi, double
     w = c->D.mrc.wbuf;
   }
   return ceig_vec_pass(c, a, 1, lo, hi, Z, w, nullptr, info, (hipStream_t)stream);
+}
+
+// Iterations it0 .. it0 + nsteps - 1 of the clique-splitting ADMM for the projection of a onto the cone of PSD-completable
+// matrices, on the state (x, U, W) in place.  An iteration: gather_all of x into D.upd, k_cone_split by slot class,
+// k_clique_scatter of W per level into cone_sw (it uses D.upd as its stack, so it comes behind the split), k_cone_update,
+// k_cone_resid into row it of hist.  Nothing is read back and nothing waits (after the first call on the context).
+int csp_cone_project_steps(csp_ctx* c, const double* a, double* x, double* U, double* W, double rho, double relax, int64_t it0,
+                           int64_t nsteps, double* hist, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!a || !x || !U || !W || !hist || !(rho > 0.0) || !(relax > 0.0 && relax < 2.0) || it0 < 0 || nsteps < 1 || c->ntrial != 1 ||
+      c->xr_world > 1)
+    return SMCP_EINVAL;
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = cone_setup(c, st)) return rc;
+  if (ranges_overlap({{x, S.blklen()}, {U, c->qlen}, {W, c->qlen}, {hist, 4 * (it0 + nsteps)}}, {{a, S.blklen()}})) return SMCP_EINVAL;
+  invalidate_tags(c, x);
+  const int64_t nsn = S.nsn;
+  const int npart = (int)cone_parts(S);
+  MrcArgs m = mrc_args(c, x, 0.0);
+  m.Q = U;
+  m.pw = W;
+  m.qptr = D.mrc.qptr;
+  m.lo = relax;
+  m.pinfo = D.mrc.cone_info;
+  TreeArgs t = tree_args(c);
+  for (int64_t it = it0; it < it0 + nsteps; ++it) {
+    gather_all(c, x, 0, 1, D.upd, st);
+    if (int rc = mrc_launch<k_cone_split>(c, KID_ceig, m, c->cone_need, 0, nsn, st, D.mrc.cone_list)) return rc;
+    for_levels_up(c, [&](const int32_t* lev, int cnt) {
+      t.lev = lev;
+      launch(c, KID_gather_level, k_clique_scatter, dim3((unsigned)cnt), dim3(MRC_NT), st, t, (const double*)W, (const int64_t*)D.mrc.qptr,
+             D.mrc.cone_sw);
+    });
+    launch(c, KID_axpby, k_cone_update, dim3((unsigned)npart), dim3(MRC_NT), st, S.blklen(), a, (const double*)D.mrc.cone_sw,
+           (const double*)D.mrc.cone_mw, rho, x, D.mrc.cone_part);
+    launch(c, KID_ceig_reduce, k_cone_resid, dim3(1), dim3(MRC_NT), st, (const double*)D.mrc.cone_info, (const int32_t*)m.rank,
+           (const int32_t*)m.flag, (int)nsn, (const double*)D.mrc.cone_part, npart, hist + 4 * it, D.mrc.cone_sweeps, it == 0 ? 1 : 0);
+  }
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// the most Jacobi sweeps of a clique in any iteration since the csp_cone_project_steps that began at it0 = 0 (waits for the
+// stream: one integer is read back)
+int csp_cone_project_sweeps(csp_ctx* c, int64_t* out, void* stream) {
+  if (int rc = ready(c)) return rc;
+  if (!out || !c->D.mrc.cone_sweeps) return SMCP_EINVAL;
+  int32_t v = 0;
+  HIPCHK(hipMemcpyAsync(&v, c->D.mrc.cone_sweeps, sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+  *out = v;
+  return 0;
 }
 
 // ---- Euclidean distance matrix completion (front_edm.hip) -----------------------------------------------------------

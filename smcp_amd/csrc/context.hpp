@@ -73,12 +73,17 @@ struct SymmPlan {
 // (front_ceig.hip) the gathered separator blocks of the second matrix of a pencil (upd2, updlen doubles, made by the first
 // pencil call) and the four extremes of a call that passes no buffer for them (ext); for the packed clique blocks the
 // offsets of the blocks (qptr, nsn + 1, made by the first call that takes or gives such blocks) and the eigenvalues of a
-// csp_clique_project that passes no buffer for them (wbuf, rowptr[nsn] doubles)
+// csp_clique_project that passes no buffer for them (wbuf, rowptr[nsn] doubles); for csp_cone_project_steps, made by its
+// first call (cone_mw marks them as made): the scatter of the W_k and the signed multiplicities (cone_sw, cone_mw, blklen
+// doubles each), per clique the negative eigenvalues and r_k^2 (cone_info, 2 nsn), the partial sums of k_cone_update
+// (cone_part), its own slot-sorted list of all cliques (cone_list) and the most sweeps so far (cone_sweeps, one int)
 struct CompletionWs {
   double* ws = nullptr; int64_t cap = 0;
   int32_t* ints = nullptr; double* xdiag = nullptr; int32_t* list = nullptr;
   double* upd2 = nullptr; double* ext = nullptr;
   int64_t* qptr = nullptr; double* wbuf = nullptr;
+  double* cone_sw = nullptr; double* cone_mw = nullptr; double* cone_info = nullptr; double* cone_part = nullptr;
+  int32_t* cone_list = nullptr; int32_t* cone_sweeps = nullptr;
 };
 
 // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
@@ -358,6 +363,7 @@ struct csp_ctx : smcp::PartitionTables {
   int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
   int64_t ceig_sweeps = 0;              // the most Jacobi sweeps a clique took in the last csp_clique_eigvalsh / _eigh / _project
   int64_t qlen = 0;                     // doubles of the packed clique blocks (set with D.mrc.qptr)
+  std::vector<int64_t> cone_need;       // slot sizes of the cliques of D.mrc.cone_list, ascending (csp_cone_project_steps)
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
   std::vector<PsdLevel> psd_lev;        // per level with fill work, root first
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy

@@ -28,6 +28,10 @@
 // k_clique_gather / k_clique_scatter: the packed clique blocks (block k: nf x nf, column-major, at qptr[k]) from a blkval
 // with its separator blocks gathered, and back: x = P_V(sum_k E_k Z_k E_k^T), one launch per level, leaves first, a clique's
 // panel and update block from the lower triangle of Z_k, then its children's update blocks by add_children (front_generic.hip).
+//
+// The projection onto the cone itself (csp_cone_project_steps): k_cone_split, the clique step of a
+// clique-splitting ADMM on top of ceig_jacobi<true>, k_cone_update, the step on the pattern, and k_cone_resid, the row of
+// residuals of an iteration; k_cone_mult makes the multiplicities once per context.  See above each of them.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -335,6 +339,173 @@ __global__ void __launch_bounds__(MRC_NT) k_ceig_vec(MrcArgs a) {
       a.flag[k] = noconv ? CEIG_NO_CONV : 0;
     }
     __syncthreads();
+  }
+}
+
+// ---- clique-splitting ADMM for the projection onto the cone of PSD-completable matrices (csp_cone_project_steps) --------
+// The clique step (k_cone_split), per clique k with the packed blocks U_k (the scaled dual, negative semidefinite) and
+// W_k = Z_k - U_k of the iteration before:
+//   T_k = Z'_k + relax (X_gg - Z'_k) + U_k,  Z'_k = W_k + U_k;   U_k <- P_-(T_k),  Z_k = T_k - U_k,  W_k <- T_k - 2 U_k.
+// The entry (i >= j) of T_k: x from the panel or the gathered separator block (the indexing of ceig_form), u and w from the
+// lower triangles of the blocks; the fused multiply-add is spelled out so that both formations of T_k give the same bits.
+__device__ inline double cone_x(const CliqueDesc& d, const double* P, const double* S, int i, int j) {
+  return j < d.nn ? P[i + (int64_t)j * (d.nn + d.na)] : S[(i - d.nn) + (int64_t)(j - d.nn) * d.na];
+}
+__device__ inline void cone_form(const CliqueDesc& d, const double* P, const double* S, const double* Uk, const double* Wk,
+                                 double relax, double* F) {
+  const int nf = d.nn + d.na;
+  for (int e = SMCP_TID; e < nf * nf; e += MRC_NT) {
+    const int i = e % nf, j = e / nf;
+    if (i >= j) {
+      const double u = Uk[e], z = Wk[e] + u;
+      const double v = fma(relax, cone_x(d, P, S, i, j) - z, z) + u;
+      F[e] = v;
+      F[j + (int64_t)i * nf] = v;
+    }
+  }
+  __syncthreads();
+}
+
+// MrcArgs: x / upd = X and its gathered separator blocks, Q = U and pw = W (packed clique blocks at qptr[k], both
+// rewritten in place), lo = relax, pinfo + 2 k = the number of negative eigenvalues of T_k and r_k^2 = |X_gg - Z_k|_F^2,
+// rank = sweeps, flag = CEIG_NO_CONV per clique.  The slot and the Jacobi are those of k_ceig_vec; then T_k is formed again
+// over F (the last reads of the old U_k and W_k, a barrier behind them) and every entry of the lower triangle is one
+// thread's sum over the negative eigenvalues, ascending, mirrored on store: a block without a negative eigenvalue leaves
+// U_k exactly 0 and W_k the bits of T_k.  A clique that did not converge leaves NaN in U_k, W_k and its two entries of pinfo.
+__global__ void __launch_bounds__(MRC_NT) k_cone_split(MrcArgs a) {
+  extern __shared__ double mrc_lds[];
+  __shared__ double red[MRC_NT];
+  __shared__ double stab[5 * CEIG_TAB_H];      // as in k_ceig
+  double* ws = a.ws ? a.ws + (int64_t)blockIdx.x * a.slot : mrc_lds;
+  for (int e = blockIdx.x; e < a.cnt; e += gridDim.x) {
+    const int k = a.lev[e];
+    const CliqueDesc d = a.cl[k];
+    const int nf = d.nn + d.na;
+    double* F = ws;
+    double* V = F + (int64_t)nf * nf;
+    double* tab = V + (int64_t)nf * nf;
+    double* dg = tab;                          // the diagonal; behind it the column of every rank (nf ints of the 2 nf of
+    int* col = (int*)(tab + nf);               // k_ceig_vec), then the sorted spectrum
+    double* sw = tab + 2 * nf;
+    const double* P = a.x + d.blk;
+    const double* S = a.upd + d.upd;
+    double* Uk = a.Q + a.qptr[k];
+    double* Wk = a.pw + a.qptr[k];
+    const double relax = a.lo;
+    cone_form(d, P, S, Uk, Wk, relax, F);
+    for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) V[t] = (t % (nf + 1) == 0) ? 1.0 : 0.0;
+    __syncthreads();
+    int noconv;
+    const int sweeps = ceig_jacobi<true>(nf, F, (nf + 1) / 2 <= CEIG_TAB_H ? stab : tab, red, &noconv, V);
+    if (!noconv) {
+      for (int i = SMCP_TID; i < nf; i += MRC_NT) dg[i] = F[i + (int64_t)i * nf];
+      __syncthreads();
+      for (int i = SMCP_TID; i < nf; i += MRC_NT) {
+        const double v = dg[i];
+        int r = 0;
+        for (int j = 0; j < nf; ++j) r += (dg[j] < v || (dg[j] == v && j < i)) ? 1 : 0;
+        sw[r] = v;
+        col[r] = i;
+      }
+      __syncthreads();
+      cone_form(d, P, S, Uk, Wk, relax, F);
+      double cn = 0.0;
+      for (int r = SMCP_TID; r < nf; r += MRC_NT) cn += sw[r] < 0.0 ? 1.0 : 0.0;
+      const int nneg = (int)ceig_reduce(cn, false, red);
+      double rs = 0.0;
+      for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) {
+        const int i = t % nf, j = t / nf;
+        if (i >= j) {
+          double u = 0.0;
+          for (int r = 0; r < nneg; ++r) {
+            const double* q = V + (int64_t)col[r] * nf;
+            u += sw[r] * (q[i] * q[j]);
+          }
+          const double tk = F[t], w = tk - 2.0 * u;
+          const double dz = cone_x(d, P, S, i, j) - (tk - u);
+          rs += i == j ? dz * dz : 2.0 * (dz * dz);
+          Uk[t] = u;
+          Uk[j + (int64_t)i * nf] = u;
+          Wk[t] = w;
+          Wk[j + (int64_t)i * nf] = w;
+        }
+      }
+      rs = ceig_reduce(rs, false, red);
+      if (SMCP_TID == 0) {
+        a.pinfo[2 * k] = (double)nneg;
+        a.pinfo[2 * k + 1] = rs;
+      }
+    } else {
+      for (int t = SMCP_TID; t < nf * nf; t += MRC_NT) Uk[t] = Wk[t] = NAN;
+      if (SMCP_TID == 0) a.pinfo[2 * k] = a.pinfo[2 * k + 1] = NAN;
+    }
+    if (SMCP_TID == 0) {
+      a.rank[k] = sweeps;
+      a.flag[k] = noconv ? CEIG_NO_CONV : 0;
+    }
+    __syncthreads();
+  }
+}
+
+// mw, the signed multiplicities: per slot of blkval the number of cliques that hold the entry, negative on the diagonal
+// of the matrix, 0 on the unused slots above the diagonal of a diagonal block.  One level of the scatter of all-ones
+// blocks (k_clique_scatter with Z = 1), the diagonal negated once the children's counts are in.
+__global__ void __launch_bounds__(MRC_NT) k_cone_mult(TreeArgs a, double* mw) {
+  const int k = a.lev[blockIdx.x];
+  const CliqueDesc d = a.cl[k];
+  const int nn = d.nn, na = d.na, nf = nn + na;
+  double* P = mw + d.blk;
+  double* Uk = a.upd + d.upd;
+  for (int e = SMCP_TID; e < nf * nn; e += MRC_NT) P[e] = e % nf >= e / nf ? 1.0 : 0.0;
+  for (int e = SMCP_TID; e < na * na; e += MRC_NT) Uk[e] = e % na >= e / na ? 1.0 : 0.0;
+  __syncthreads();
+  add_children(a, d, a.upd, P, Uk, 1.0, 1.0);
+  for (int j = SMCP_TID; j < nn; j += MRC_NT) P[j + (int64_t)j * nf] = -P[j + (int64_t)j * nf];
+}
+
+// The update on the pattern: x <- (a + rho sw) / (1 + rho |mw|) with sw = the scatter of the W_k, zeros on the unused slots
+// whatever a and x hold there; part[blockIdx.x] = this workgroup's share of |x_new - x_old|^2 in the norm of csp_dot (1 on
+// the diagonal, 2 off it), summed in a fixed tree.  The grid is a function of len alone.
+__global__ void __launch_bounds__(MRC_NT) k_cone_update(int64_t len, const double* a, const double* sw, const double* mw, double rho,
+                                                         double* x, double* part) {
+  __shared__ double red[MRC_NT];
+  double acc = 0.0;
+  for (int64_t e = (int64_t)blockIdx.x * MRC_NT + SMCP_TID; e < len; e += (int64_t)gridDim.x * MRC_NT) {
+    const double m = mw[e];
+    double v = 0.0;
+    if (m != 0.0) {
+      v = (a[e] + rho * sw[e]) / (1.0 + rho * fabs(m));
+      const double dx = v - x[e];
+      acc += m < 0.0 ? dx * dx : 2.0 * (dx * dx);
+    }
+    x[e] = v;
+  }
+  acc = ceig_reduce(acc, false, red);
+  if (SMCP_TID == 0) part[blockIdx.x] = acc;
+}
+
+// One row of the history: hist[0] = sum_k r_k^2, hist[1] = the sum of the npart partial sums of k_cone_update,
+// hist[2] = the negative eigenvalues over all cliques, hist[3] = 1 + the lowest clique that did not converge (0: none);
+// every sum one thread's strided loop and the tree of ceig_reduce.  msw: the most sweeps of a clique since the call with
+// reset set.
+__global__ void __launch_bounds__(MRC_NT) k_cone_resid(const double* pinfo, const int32_t* sweeps, const int32_t* flag, int nsn,
+                                                        const double* part, int npart, double* hist, int32_t* msw, int reset) {
+  __shared__ double red[MRC_NT];
+  double r2 = 0.0, ng = 0.0, s2 = 0.0, best;
+  for (int k = SMCP_TID; k < nsn; k += MRC_NT) { ng += pinfo[2 * k]; r2 += pinfo[2 * k + 1]; }
+  for (int p = SMCP_TID; p < npart; p += MRC_NT) s2 += part[p];
+  r2 = ceig_reduce(r2, false, red);
+  ng = ceig_reduce(ng, false, red);
+  s2 = ceig_reduce(s2, false, red);
+  const int ncv = mrc_argmax(nsn, [&](int k) { return flag[k] == CEIG_NO_CONV ? -(double)k : -INFINITY; }, best);
+  const int sw = mrc_argmax(nsn, [&](int k) { return (double)sweeps[k]; }, best);
+  if (SMCP_TID == 0) {
+    hist[0] = r2;
+    hist[1] = s2;
+    hist[2] = ng;
+    hist[3] = ncv >= 0 ? (double)(ncv + 1) : 0.0;
+    const int most = sw >= 0 ? sweeps[sw] : 0, before = reset ? 0 : *msw;
+    *msw = most > before ? most : before;
   }
 }
 

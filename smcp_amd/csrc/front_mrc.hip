@@ -54,6 +54,8 @@ struct MrcArgs {
   double lo, hi;            // eigenvalues changed and the squared distance at pinfo + 2 k
   double* pinfo;
   int vmode;
+  // k_cone_split reads these differently: Q = U and pw = W (packed clique blocks, rewritten in place), lo = the
+  // over-relaxation, pinfo + 2 k = the negative eigenvalues and the squared primal residual of clique k
 };
 
 // (value, index) of the largest val(i), i < n; ties go to the lowest index, -1 when every value is -inf / NaN.  The
