@@ -81,7 +81,10 @@ enum {
                              more pivots above the threshold than the r columns left room for (0 when r came from
                              csp_mrcompletion_rank with the same X and tol, up to rounding) */
   CSP_Q_EDM_CLAMPED = 19, /* 1 value: the same for the last csp_edmcompletion (r from csp_edmcompletion_rank) */
-  CSP_Q_CEIG_SWEEPS = 20  /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh, csp_clique_eigh or
+  CSP_Q_CEIG_SWEEPS = 20, /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh, csp_clique_eigh or
+                             csp_clique_project on this context; for a clique on the wide route (CSP_TUNE_CEIG_WIDE) its BLOCK
+                             sweeps are what is counted */
+  CSP_Q_CEIG_WIDE = 21    /* 1 value: the cliques that took the wide route in the last csp_clique_eigvalsh, csp_clique_eigh or
                              csp_clique_project on this context */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
@@ -251,7 +254,9 @@ int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd
  * smallest eigenvalue over all cliques, the lowest clique attaining it, the largest, and the lowest clique attaining that.
  * One workgroup per clique: a Cholesky of B_gg and two triangular solves (pencil form), a two-sided cyclic Jacobi in a
  * fixed parallel order without eigenvectors, a rank sort; at most six launches plus one whatever the tree, beside the
- * top-down gathers of the separator blocks.  The same input gives the same bits.  Returns 0, 1 + k when B_gg of clique k
+ * top-down gathers of the separator blocks (in standard form under CSP_TUNE_CEIG_WIDE the wide cliques leave these launches
+ * for a block Jacobi over the whole chip: two launches per step of a block sweep, one integer read back per block sweep).
+ * The same input gives the same bits.  Returns 0, 1 + k when B_gg of clique k
  * is not positive definite, SMCP_ENOCONV when a clique did not converge in 30 sweeps (a non-finite entry ends this way),
  * SMCP_EINVAL for a null a or w, a replicated context, or w / ext overlapping a, b or each other.  The most sweeps of a
  * clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back; w and ext are not). */
@@ -276,7 +281,8 @@ int csp_clique_scatter(csp_ctx* ctx, const double* Z, double* x, void* stream);
  * (device, packed clique blocks): column j of block k is a unit eigenvector of A_gg for w[rowptr[k] + j].  The Jacobi
  * iteration of csp_clique_eigvalsh with the rotations accumulated, in the slot of its pencil form; signs and the basis
  * inside a degenerate eigenspace are unspecified but repeatable: the same input gives the same bits.  A clique wider
- * than 89 rows runs from a slot in device memory on one workgroup and is slow.  Returns 0, SMCP_ENOCONV when a clique did
+ * than 89 rows runs from a slot in device memory on one workgroup and is slow unless CSP_TUNE_CEIG_WIDE sends it through the
+ * chip-wide block Jacobi.  Returns 0, SMCP_ENOCONV when a clique did
  * not converge in 30 sweeps (a non-finite entry ends this way; w and Q of that clique are NaN, the others correct),
  * SMCP_EINVAL for a null a, w or Q, a replicated context, or w / Q / ext overlapping a or each other.  The most sweeps of
  * a clique: csp_symbolic_query(CSP_Q_CEIG_SWEEPS).  Synchronises the stream (the status is read back). */
@@ -610,6 +616,15 @@ int csp_touch(csp_ctx* ctx, const void* ptr);
                                      recorded, the caller's stream does not wait for it): results are WRONG by design and must
                                      change under CSP_TUNE_RACE, which is what tests/test_gpu_parity.py asserts.  0: back to normal
                                      (waits for the device).  PROCESS-wide. */
+#define CSP_TUNE_CEIG_WIDE 7      /* per context: the smallest order of a clique whose spectrum in standard form
+                                     (csp_clique_eigvalsh without b, csp_clique_eigh, csp_clique_project) is computed by the
+                                     chip-wide block Jacobi of front_ceigw.hip (pivots of two 32-column blocks on one workgroup
+                                     each, 64 x 64 tile products on the matrix cores over all compute units) instead of one
+                                     workgroup per clique; 0 (default): never.  1 .. 64 and negative values: SMCP_EINVAL (the
+                                     route needs three blocks).  The pencil form and csp_cone_project_steps ignore it.  With 0
+                                     every call gives the bits it gave before the route existed; with it set, results are
+                                     still the same bits from call to call.  Recommended value: 65 (the smallest
+                                     scanned value at which the route was not slower than 0 on config 4 and on synth50k) */
 int csp_tune(csp_ctx* ctx, int what, int64_t value);
 /* out[0], out[1]: milliseconds of the store-pattern probe of the last CSP_TUNE_PLACEMENT before / after (zeros: not run);
  * out[2]: delay kernels injected so far in this process (CSP_TUNE_RACE).  out holds three doubles. */

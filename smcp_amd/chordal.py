@@ -44,6 +44,7 @@ def lazy_status(symb, on=True):
 
 
 TUNE_LEAFGRAM, TUNE_VERIFY_CACHE, TUNE_DETERMINISTIC, TUNE_PLACEMENT, TUNE_RACE, TUNE_RACE_DROP_JOINS = 1, 2, 3, 4, 5, 6
+TUNE_CEIG_WIDE = 7
 
 
 def tune(symb, what, value):
@@ -53,7 +54,13 @@ def tune(symb, what, value):
     TUNE_DETERMINISTIC (1: fixed-order summation, bit-identical results from run to run), TUNE_PLACEMENT (an action: value =
     tries; after the constraints are set, moves the packed exchange buffer to the fastest of up to `tries` fresh allocations
     for the store pattern of the family sweep -- for runs of many Newton steps on one problem), TUNE_RACE (value = seed,
-    0 = off, process-wide: seeded delay injection on every internal stream hand-over, tools/race_hunt.sh)."""
+    0 = off, process-wide: seeded delay injection on every internal stream hand-over, tools/race_hunt.sh).
+
+    TUNE_CEIG_WIDE (per Symbolic; value = the smallest order of a clique that takes the wide route, 0 = never, the default;
+    1 .. 64 and negative values are refused: RuntimeError, invalid argument): ``clique_eigvalsh`` without B, ``cone_margin``, ``clique_eigh`` and
+    ``clique_project`` diagonalise such cliques by a block Jacobi spread over the whole chip (csrc/front_ceigw.hip) instead of
+    one workgroup per clique.  ``max_step`` (the pencil form) and ``cone_project`` ignore it.  ``clique_eig_wide`` tells how
+    many cliques took the route, and ``clique_eig_sweeps`` counts block sweeps for them."""
     _ensure(symb)
     _chk(_lib.lib().csp_tune(symb.handle, int(what), int(value)), "csp_tune")
 
@@ -221,9 +228,17 @@ def clique_extremes(A, B=None):
 
 def clique_eig_sweeps(symb):
     """The most Jacobi sweeps any clique took in the last ``clique_eigvalsh``, ``clique_eigh`` or ``clique_project`` on symb
-    (CSP_Q_CEIG_SWEEPS)."""
+    (CSP_Q_CEIG_SWEEPS); for a clique on the wide route (TUNE_CEIG_WIDE) its block sweeps are counted."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 20, ctypes.byref(out))
+    return out.value
+
+
+def clique_eig_wide(symb):
+    """The number of cliques that took the wide route (``tune(symb, TUNE_CEIG_WIDE, order)``) in the last ``clique_eigvalsh``,
+    ``clique_eigh`` or ``clique_project`` on symb (CSP_Q_CEIG_WIDE)."""
+    out = ctypes.c_int64(0)
+    _lib.lib().csp_symbolic_query(symb.handle, 21, ctypes.byref(out))
     return out.value
 
 
@@ -323,7 +338,7 @@ def clique_eigh(A):
     Signs and the basis inside a degenerate eigenspace are unspecified, but the same input gives the same bits.  A is
     not written.  RuntimeError when a clique did not converge in 30 Jacobi sweeps (a non-finite entry ends this way).
     A clique wider than 89 rows does not fit the on-chip memory of its workgroup and is slow: one workgroup works on it
-    from device memory (csp_clique_eigh)."""
+    from device memory, unless ``tune(symb, TUNE_CEIG_WIDE, 65)`` sends it through the chip-wide block Jacobi (csp_clique_eigh)."""
     symb = A.symb
     _ensure(symb)
     dev = A.blkval.device

@@ -40,6 +40,7 @@
 #include "front_edm.hip"
 #include "front_psd.hip"
 #include "front_ceig.hip"
+#include "front_ceigw.hip"
 #include "front_trmm.hip"
 #include "front_syr2k.hip"
 #include "front_symm.hip"
@@ -2168,6 +2169,9 @@ int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
     case CSP_Q_CEIG_SWEEPS:
       if (out) out[0] = c->ceig_sweeps;
       return 1;
+    case CSP_Q_CEIG_WIDE:
+      if (out) out[0] = c->ceig_wide_count;
+      return 1;
   }
   return SMCP_EINVAL;
 }
@@ -2925,6 +2929,10 @@ int csp_tune(csp_ctx* c, int what, int64_t value) {
       return 0;
     case CSP_TUNE_DETERMINISTIC:
       c->deterministic = value != 0;
+      return 0;
+    case CSP_TUNE_CEIG_WIDE:
+      if (value < 0 || (value > 0 && value <= 2 * CW_B)) return SMCP_EINVAL;      // the block Jacobi needs three blocks
+      c->ceig_wide = value;
       return 0;
     case CSP_TUNE_RACE:
       if (value < 0) return SMCP_EINVAL;

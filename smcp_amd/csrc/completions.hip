@@ -239,6 +239,74 @@ bool ranges_overlap(std::initializer_list<DRange> outs, std::initializer_list<DR
   return false;
 }
 
+// ---- wide cliques on the whole chip (front_ceigw.hip) ---------------------------------------------------------------
+// the clique takes the block Jacobi under this context's CSP_TUNE_CEIG_WIDE
+bool ceig_is_wide(const csp_ctx* c, int64_t k) { return c->ceig_wide > 0 && c->S.nf(k) >= c->ceig_wide; }
+
+// One launch group of wide cliques: form, then block sweeps until no clique of the group runs (one integer read back per
+// sweep), then the rank sort and the output blocks.  m.rank / m.flag of these cliques are filled as k_ceig fills them.
+int ceigw_group(csp_ctx* c, CeigwArgs a, const std::vector<CeigwDesc>& desc, int64_t doubles, hipStream_t st) {
+  DeviceCtx& D = c->D;
+  if (lds_ceiling<k_ceigw_pivot>() < (int64_t)CW_PIVOT_LDS + 4096 || lds_ceiling<k_ceigw_apply>() < (int64_t)CW_APPLY_LDS + 4096) return SMCP_EHIP;
+  const int nw = (int)desc.size();
+  if (int rc = dev_grow(&D.mrc.wws, &D.mrc.wcap, doubles, D.mem, st)) return rc;
+  if (int rc = dev_grow(&D.mrc.wdesc, &D.mrc.wdesc_cap, (int64_t)nw, D.mem, st)) return rc;
+  HIPCHK(hipMemcpyAsync(D.mrc.wdesc, desc.data(), nw * sizeof(CeigwDesc), hipMemcpyHostToDevice, st));
+  a.wd = D.mrc.wdesc;
+  a.ws = D.mrc.wws;
+  a.nw = nw;
+  a.nrun = D.mrc.ints + 2 * c->S.nsn + 3;
+  int hmax = 0, nbmax = 0;
+  int64_t nfmax = 0;
+  for (const CeigwDesc& w : desc) { hmax = std::max(hmax, (int)w.h); nbmax = std::max(nbmax, (int)w.nb); nfmax = std::max<int64_t>(nfmax, w.nf); }
+  const int steps = nbmax + (nbmax & 1) - 1;
+  const unsigned parts = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, nfmax * nfmax / (MRC_NT * 32)));
+  const unsigned tiles = (unsigned)(hmax * (hmax + 1) / 2 + (a.vec ? (int)((nfmax + CW_T - 1) / CW_T) * hmax : 0));
+  launch(c, KID_ceig, k_ceigw_form, dim3(parts, (unsigned)nw), dim3(MRC_NT), st, a);
+  launch(c, KID_ceig, k_ceigw_begin, dim3((unsigned)nw), dim3(MRC_NT), st, a);
+  for (;;) {
+    launch(c, KID_ceig_reduce, k_ceigw_check, dim3(1), dim3(MRC_NT), st, a);
+    int32_t nrun = 0;
+    HIPCHK(hipMemcpyAsync(&nrun, a.nrun, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nrun <= 0) break;
+    for (int r = 0; r < steps; ++r) {
+      launch_lds(c, KID_ceig, k_ceigw_pivot, dim3((unsigned)hmax, (unsigned)nw), dim3(MRC_NT), CW_PIVOT_LDS, st, a, r);
+      launch_lds(c, KID_ceig, k_ceigw_apply, dim3(tiles, (unsigned)nw), dim3(MRC_NT), CW_APPLY_LDS, st, a, r, hmax);
+    }
+  }
+  launch(c, KID_ceig, k_ceigw_sort, dim3((unsigned)nw), dim3(MRC_NT), st, a);
+  if (a.vec) launch(c, KID_ceig, k_ceigw_out, dim3(parts, (unsigned)nw), dim3(MRC_NT), st, a);
+  return 0;
+}
+
+// The wide cliques of a call (ascending), in groups whose workspace stays within MRC_HBM_DOUBLES (always at least one clique)
+int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
+  const Symbolic& S = c->S;
+  CeigwArgs a{};
+  a.m = m;
+  a.vec = vec ? 1 : 0;
+  std::vector<CeigwDesc> desc;
+  int64_t doubles = 0;
+  c->ceig_wide_count = 0;
+  for (int64_t k = 0; k < S.nsn; ++k) {
+    if (!ceig_is_wide(c, k)) continue;
+    ++c->ceig_wide_count;
+    CeigwDesc w;
+    int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, doubles);
+    if (!desc.empty() && doubles + len > MRC_HBM_DOUBLES) {
+      if (int rc = ceigw_group(c, a, desc, doubles, st)) return rc;
+      desc.clear();
+      doubles = 0;
+      len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, 0);
+    }
+    desc.push_back(w);
+    doubles += len;
+  }
+  if (!desc.empty()) return ceigw_group(c, a, desc, doubles, st);
+  return 0;
+}
+
 // csp_clique_eigh (vmode 0) and csp_clique_project (vmode 1): the launches of csp_clique_eigvalsh in standard form with
 // k_ceig_vec in the slots of the pencil form, under the same kernel ids; ext null: the context's own four doubles
 int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, double* Q, double* w, double* ext, double* info,
@@ -250,7 +318,8 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
   if (!ext && !D.mrc.ext)
     if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
   std::vector<int64_t> need, ranges;
-  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return ceig_slot2(S.nf(k)); }, need, ranges, st)) return rc;
+  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return ceig_is_wide(c, k) ? (int64_t)-1 : ceig_slot2(S.nf(k)); }, need, ranges, st))
+    return rc;
   gather_all(c, a, 0, 1, D.upd, st);
   MrcArgs m = mrc_args(c, a, 0.0);
   m.w = w;
@@ -260,7 +329,8 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
   m.hi = hi;
   m.pinfo = info;
   m.vmode = vmode;
-  if (int rc = mrc_launch<k_ceig_vec>(c, KID_ceig, m, need, 0, nsn, st)) return rc;
+  if (int rc = mrc_launch<k_ceig_vec>(c, KID_ceig, m, need, 0, (int64_t)need.size(), st)) return rc;
+  if (int rc = ceigw_pass(c, m, true, st)) return rc;
   int32_t* dout = D.mrc.ints + 2 * nsn;
   launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
          (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);
@@ -359,7 +429,9 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   if (!ext && !D.mrc.ext)
     if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
   std::vector<int64_t> need, ranges;
-  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return b ? ceig_slot2(S.nf(k)) : ceig_slot1(S.nf(k)); }, need, ranges, st))
+  // the wide cliques of the standard form leave the list for the block Jacobi of front_ceigw.hip (the pencil form ignores the tune)
+  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return b ? ceig_slot2(S.nf(k)) : ceig_is_wide(c, k) ? (int64_t)-1 : ceig_slot1(S.nf(k)); },
+                                 need, ranges, st))
     return rc;
   gather_all(c, a, 0, 1, D.upd, st);
   if (b) gather_all(c, b, 0, 1, D.mrc.upd2, st);
@@ -367,7 +439,10 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   m.x2 = b;
   m.upd2 = D.mrc.upd2;
   m.w = w;
-  if (int rc = mrc_launch<k_ceig>(c, KID_ceig, m, need, 0, nsn, st)) return rc;
+  if (int rc = mrc_launch<k_ceig>(c, KID_ceig, m, need, 0, (int64_t)need.size(), st)) return rc;
+  c->ceig_wide_count = 0;
+  if (!b)
+    if (int rc = ceigw_pass(c, m, false, st)) return rc;
   int32_t* dout = D.mrc.ints + 2 * nsn;
   launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
          (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);
