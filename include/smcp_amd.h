@@ -84,8 +84,8 @@ enum {
   CSP_Q_CEIG_SWEEPS = 20, /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh, csp_clique_eigh or
                              csp_clique_project on this context; for a clique on the wide route (CSP_TUNE_CEIG_WIDE) its BLOCK
                              sweeps are what is counted */
-  CSP_Q_CEIG_WIDE = 21    /* 1 value: the cliques that took the wide route in the last csp_clique_eigvalsh, csp_clique_eigh or
-                             csp_clique_project on this context */
+  CSP_Q_CEIG_WIDE = 21    /* 1 value: the cliques that took the wide route in the last csp_clique_eigvalsh, csp_clique_eigh,
+                             csp_clique_project or csp_cone_project_steps on this context */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -313,11 +313,17 @@ int csp_clique_project(csp_ctx* ctx, const double* a, double lo, double hi, doub
  * without a negative eigenvalue leaves U_k exactly 0.  At the fixed point x is the projection and x - a = -rho sum_k E_k U_k E_k^T
  * lies in the dual cone, the positive semidefinite matrices on the pattern.  Every sum in a fixed order, no atomics: the same
  * input gives the same bits, and 1 + 2 steps in two calls are the 3 steps of one.  A clique wider than 89 rows runs on one
- * workgroup from device memory, in every iteration.  Does not synchronise and reads nothing back (the first call on a context
- * builds the workspace and may wait).  SMCP_EINVAL for a null pointer, any overlap among a, x, U, W and hist, rho <= 0, relax
- * outside (0, 2), it0 < 0, nsteps < 1, a replicated or partitioned context.
- * csp_cone_project_sweeps: *out (host) = the most Jacobi sweeps of a clique in any iteration since the call with it0 = 0;
- * waits for the stream.  SMCP_EINVAL before the first csp_cone_project_steps on the context. */
+ * workgroup from device memory, in every iteration, unless CSP_TUNE_CEIG_WIDE sends it through the chip-wide block Jacobi:
+ * per iteration and launch group of wide cliques the form, 30 block sweeps with the stop test in front of each and one behind
+ * the last, the rank sort and the split -- a number of launches that depends on the pattern and the tune alone; the launches
+ * behind the test that ended a clique return at once.  hist[4 it + 3] names a wide clique that 30 block sweeps did not
+ * finish as it names the others.  Does not synchronise and reads nothing back (the first call on a context, and the first
+ * after the tune changed, builds the workspace and may wait).  SMCP_EINVAL for a null pointer, any overlap among a, x, U, W
+ * and hist, rho <= 0, relax outside (0, 2), it0 < 0, nsteps < 1, a replicated or partitioned context; SMCP_EHIP when the
+ * device does not grant the wide route its 128 KiB of LDS.
+ * csp_cone_project_sweeps: *out (host) = the most sweeps of a clique in any iteration since the call with it0 = 0 (Jacobi
+ * sweeps, or block sweeps of a clique on the wide route); waits for the stream.  SMCP_EINVAL before the first
+ * csp_cone_project_steps on the context. */
 int csp_cone_project_steps(csp_ctx* ctx, const double* a, double* x, double* U, double* W, double rho, double relax, int64_t it0,
                            int64_t nsteps, double* hist, void* stream);
 int csp_cone_project_sweeps(csp_ctx* ctx, int64_t* out, void* stream);
@@ -621,7 +627,9 @@ int csp_touch(csp_ctx* ctx, const void* ptr);
                                      chip-wide block Jacobi of front_ceigw.hip (pivots of two 32-column blocks on one workgroup
                                      each, 64 x 64 tile products on the matrix cores over all compute units) instead of one
                                      workgroup per clique; 0 (default): never.  1 .. 64 and negative values: SMCP_EINVAL (the
-                                     route needs three blocks).  The pencil form and csp_cone_project_steps ignore it.  With 0
+                                     route needs three blocks).  csp_cone_project_steps sends the same cliques through it in
+                                     every iteration, by a fixed chain of launches that reads nothing back; the first call
+                                     after the value changed builds its lists again and may wait.  The pencil form ignores it.  With 0
                                      every call gives the bits it gave before the route existed; with it set, results are
                                      still the same bits from call to call.  Recommended value: 65 (the smallest
                                      scanned value at which the route was not slower than 0 on config 4 and on synth50k) */

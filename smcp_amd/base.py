@@ -552,14 +552,22 @@ def cone_margin(X):
     return chordal.cone_margin(_on_chordal_pattern([X], "cone_margin")[0])[0]
 
 
-def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, return_info=False):
+def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, return_info=False, wide=0):
     """The nearest matrix to the sparse symmetric A (scipy sparse, either triangle or both) on its chordal pattern that has a
     positive semidefinite completion (cone="primal") or is itself positive semidefinite (cone="dual"), in the Frobenius norm:
     a symmetric scipy CSC matrix in the coordinates of A (smcp_amd.chordal.cone_project; read its docstring for what kind
     of input the iteration is for).  return_info=True: (X, info) with the dict of that call, without the device tensors `hist`
-    and `U`.  ValueError for a pattern that is not chordal."""
+    and `U`.  wide: the smallest order of a clique whose eigen work runs on the whole chip in every iteration
+    (``chordal.tune(symb, TUNE_CEIG_WIDE, wide)`` on the Symbolic this call builds; 65 for a pattern with a clique of a
+    hundred rows or more); 0, the default, sends none there.  ValueError for a pattern that is not chordal and for a `wide`
+    in 1 .. 64 or below 0."""
     from . import chordal
+    wide = int(wide)
+    if wide < 0 or 1 <= wide <= 64:
+        raise ValueError("cone_project: wide must be 0 or at least 65")
     Ac = _on_chordal_pattern([A], "cone_project")[0]
+    if wide:                                    # (0: the default path as it was, the Symbolic is new and its tune is 0)
+        chordal.tune(Ac.symb, chordal.TUNE_CEIG_WIDE, wide)
     out = chordal.cone_project(Ac, cone=cone, tol=tol, maxit=maxit, rho=rho, relax=relax, return_info=return_info)
     if not return_info:
         return out.spmatrix(reordered=False, symmetric=True)

@@ -59,7 +59,8 @@ def tune(symb, what, value):
     TUNE_CEIG_WIDE (per Symbolic; value = the smallest order of a clique that takes the wide route, 0 = never, the default;
     1 .. 64 and negative values are refused: RuntimeError, invalid argument): ``clique_eigvalsh`` without B, ``cone_margin``, ``clique_eigh`` and
     ``clique_project`` diagonalise such cliques by a block Jacobi spread over the whole chip (csrc/front_ceigw.hip) instead of
-    one workgroup per clique.  ``max_step`` (the pencil form) and ``cone_project`` ignore it.  ``clique_eig_wide`` tells how
+    one workgroup per clique, and so does every iteration of ``cone_project`` (a fixed chain of launches per iteration, with
+    nothing read back; its ``info["wide"]``).  ``max_step`` (the pencil form) ignores it.  ``clique_eig_wide`` tells how
     many cliques took the route, and ``clique_eig_sweeps`` counts block sweeps for them."""
     _ensure(symb)
     _chk(_lib.lib().csp_tune(symb.handle, int(what), int(value)), "csp_tune")
@@ -236,7 +237,7 @@ def clique_eig_sweeps(symb):
 
 def clique_eig_wide(symb):
     """The number of cliques that took the wide route (``tune(symb, TUNE_CEIG_WIDE, order)``) in the last ``clique_eigvalsh``,
-    ``clique_eigh`` or ``clique_project`` on symb (CSP_Q_CEIG_WIDE)."""
+    ``clique_eigh``, ``clique_project`` or ``cone_project`` on symb (CSP_Q_CEIG_WIDE)."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 21, ctypes.byref(out))
     return out.value
@@ -423,12 +424,17 @@ def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, U0=N
     symmetric entries on a band, say) can take thousands, and so can the noisy kind on a pattern of thousands of cliques
     (DESIGN.md section 21, 8073 cliques: 1e-4 after 16 iterations, 1e-5 after 428, 1e-6 after 1998).  Reaching maxit is not an error: the call returns what it has with converged False.  An A inside
     K comes back bit for bit after one iteration.  Wide cliques are slow, now in every iteration: beyond 89 rows one
-    workgroup works on the block from device memory, and with a root of several hundred rows the call is not usable.
+    workgroup works on the block from device memory, and with a root of several hundred rows the call is not usable --
+    unless ``tune(A.symb, TUNE_CEIG_WIDE, 65)`` sends the cliques of at least that order through the chip-wide block Jacobi
+    (csrc/front_ceigw.hip) in every iteration: a fixed chain of launches, nothing read back inside a chunk.  With the tune
+    at 0 (the default), or with no clique that wide, the call gives the bits it gives without it.
 
     return_info=True: (X, info) with iterations, converged, primal and dual (the residuals over max(1, |A|)), distance
     (|X - A|), hist (a device tensor (iterations, 4): the squares of the two residuals, the negative eigenvalues of all T_k,
     1 + the lowest clique that failed), U (the packed scaled duals, each block negative semidefinite, the U0 of a later call
-    with the same rho on a nearby A, which then starts from X = A - rho sum_k E_k U0_k E_k^T) and sweeps (the most Jacobi sweeps of a clique in any iteration).
+    with the same rho on a nearby A, which then starts from X = A - rho sum_k E_k U0_k E_k^T), sweeps (the most sweeps of a
+    clique in any iteration: Jacobi sweeps, or block sweeps of a clique on the wide route, whichever is larger) and wide (the
+    number of cliques that took the wide route).
     ValueError for rho <= 0, relax outside (0, 2), tol < 0, maxit < 1, another `cone`, or a U0 that is not a packed block
     tensor on the device of A; NotImplementedError on a replicated or sharded Symbolic; RuntimeError naming the clique when a
     Jacobi iteration did not converge (a non-finite entry of A ends this way), seen at the next look."""
@@ -472,8 +478,8 @@ def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, U0=N
         bad = torch.nonzero(rows[:, 3])
         if len(bad):
             i = int(bad[0])
-            raise RuntimeError("cone_project: the Jacobi iteration of clique %d did not converge in 30 sweeps at iteration %d (a "
-                               "non-finite entry?)" % (int(rows[i, 3]) - 1, it0 + i + 1))
+            raise RuntimeError("cone_project: the Jacobi iteration of clique %d did not converge in 30 sweeps (block sweeps on the "
+                               "wide route) at iteration %d (a non-finite entry?)" % (int(rows[i, 3]) - 1, it0 + i + 1))
         r2, s2 = float(rows[-1, 0]), float(rows[-1, 1])
         if it0 == 0 and U0 is None and float(rows[0, 2]) == 0.0:       # A is inside the cone: its own bits
             X.blkval.copy_(a.blkval)
@@ -491,7 +497,7 @@ def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, U0=N
     d = X.blkval - torch.where(used, A.blkval, zero)
     return X, {"iterations": done, "converged": converged, "primal": math.sqrt(float(rows[-1, 0])) / scale,
                "dual": math.sqrt(float(rows[-1, 1])) / scale, "distance": math.sqrt(float((wt * d * d).sum())),
-               "hist": hist[:done], "U": U, "sweeps": int(sw.value)}
+               "hist": hist[:done], "U": U, "sweeps": int(sw.value), "wide": clique_eig_wide(symb)}
 
 
 LANCZOS_JMAX = 128    # csrc/front_lanczos.hip: LZ_JMAX

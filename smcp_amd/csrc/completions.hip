@@ -346,22 +346,16 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
 // workgroups of k_cone_update, which is also the number of its partial sums: a function of blklen alone
 int64_t cone_parts(const Symbolic& S) { return std::max<int64_t>(1, std::min<int64_t>(1024, (S.blklen() + 4 * MRC_NT - 1) / (4 * MRC_NT))); }
 
-// What csp_cone_project_steps keeps for the life of the context, made by its first call (with synchronous uploads):
-// the workspace of CompletionWs, the slot-sorted list of all cliques with its slot sizes (a list of its own: D.mrc.list
-// belongs to whichever call runs) and the signed multiplicities, by one launch of k_cone_mult per level, leaves first
+// What csp_cone_project_steps keeps for the life of the context, made by its first call: the workspace of CompletionWs,
+// room for its list of cliques (a list of its own: D.mrc.list belongs to whichever call runs; filled by cone_route) and
+// the signed multiplicities, by one launch of k_cone_mult per level, leaves first
 int cone_setup(csp_ctx* c, hipStream_t st) {
   const Symbolic& S = c->S;
   DeviceCtx& D = c->D;
   if (int rc = mrc_setup(c)) return rc;
   if (int rc = qptr_setup(c)) return rc;
   if (D.mrc.cone_mw) return 0;
-  std::vector<std::pair<int64_t, int32_t>> tmp;
-  for (int64_t k : S.levidx) tmp.push_back({ceig_slot2(S.nf(k)), (int32_t)k});
-  std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-  std::vector<int32_t> list;
-  c->cone_need.clear();
-  for (auto& t : tmp) { c->cone_need.push_back(t.first); list.push_back(t.second); }
-  if (int rc = dev_upload(&D.mrc.cone_list, list, D.mem)) return rc;
+  if (int rc = dev_alloc(&D.mrc.cone_list, S.nsn, D.mem)) return rc;
   if (int rc = dev_alloc(&D.mrc.cone_sw, S.blklen(), D.mem)) return rc;
   if (int rc = dev_alloc(&D.mrc.cone_info, 2 * S.nsn, D.mem)) return rc;
   if (int rc = dev_alloc(&D.mrc.cone_part, cone_parts(S), D.mem)) return rc;
@@ -376,6 +370,95 @@ int cone_setup(csp_ctx* c, hipStream_t st) {
   HIPCHK(hipMemsetAsync(D.mrc.cone_sweeps, 0, sizeof(int32_t), st));
   D.mrc.cone_mw = mw;                    // last: marks the workspace as made
   return 0;
+}
+
+// Which clique takes which route in csp_cone_project_steps, made by the first call under a value of CSP_TUNE_CEIG_WIDE and
+// again when a call sees another value (c->cone_wide; it waits for the device and uploads synchronously): the slot-sorted
+// list of the cliques of k_cone_split with its slot sizes -- all cliques at 0, which is the list of a context never tuned --
+// and, for the wide ones, their descriptors (with V) in launch groups within MRC_HBM_DOUBLES, kept on the device, the
+// workspace of the largest group and the buffer of their eigenvalues.  SMCP_EHIP without the 128 KiB LDS class.
+int cone_route(csp_ctx* c, hipStream_t st) {
+  const Symbolic& S = c->S;
+  DeviceCtx& D = c->D;
+  if (c->cone_wide == c->ceig_wide) return 0;
+  c->cone_wide = -1;
+  HIPCHK(hipDeviceSynchronize());        // launches of earlier calls, on whatever stream, may still read the lists
+  std::vector<std::pair<int64_t, int32_t>> tmp;
+  for (int64_t k : S.levidx)
+    if (!ceig_is_wide(c, k)) tmp.push_back({ceig_slot2(S.nf(k)), (int32_t)k});
+  std::stable_sort(tmp.begin(), tmp.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+  std::vector<int32_t> list;
+  c->cone_need.clear();
+  for (auto& t : tmp) { c->cone_need.push_back(t.first); list.push_back(t.second); }
+  if (!list.empty()) HIPCHK(hipMemcpy(D.mrc.cone_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  std::vector<CeigwDesc> desc;
+  c->cone_groups.clear();
+  int64_t doubles = 0, most = 0;
+  for (int64_t k = 0; k < S.nsn; ++k) {
+    if (!ceig_is_wide(c, k)) continue;
+    CeigwDesc w;
+    int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), true, doubles);
+    if (c->cone_groups.empty() || (c->cone_groups.back().nw > 0 && doubles + len > MRC_HBM_DOUBLES)) {
+      csp_ctx::ConeGroup g;
+      g.first = (int)desc.size();
+      c->cone_groups.push_back(g);
+      doubles = 0;
+      len = ceigw_layout(w, (int32_t)k, S.nf(k), true, 0);
+    }
+    csp_ctx::ConeGroup& g = c->cone_groups.back();
+    ++g.nw;
+    g.hmax = std::max(g.hmax, (int)w.h);
+    g.nbmax = std::max(g.nbmax, (int)w.nb);
+    g.nfmax = std::max<int64_t>(g.nfmax, w.nf);
+    desc.push_back(w);
+    doubles += len;
+    most = std::max(most, doubles);
+  }
+  if (!desc.empty()) {
+    if (lds_ceiling<k_ceigw_pivot>() < (int64_t)CW_PIVOT_LDS + 4096 || lds_ceiling<k_ceigw_apply>() < (int64_t)CW_APPLY_LDS + 4096) return SMCP_EHIP;
+    if (int rc = dev_grow(&D.mrc.cone_wdesc, &D.mrc.cone_wdesc_cap, (int64_t)desc.size(), D.mem, st)) return rc;
+    HIPCHK(hipMemcpy(D.mrc.cone_wdesc, desc.data(), desc.size() * sizeof(CeigwDesc), hipMemcpyHostToDevice));
+    if (int rc = dev_grow(&D.mrc.wws, &D.mrc.wcap, most, D.mem, st)) return rc;
+    if (!D.mrc.wbuf)
+      if (int rc = dev_alloc(&D.mrc.wbuf, S.rowptr[S.nsn], D.mem)) return rc;
+  }
+  c->cone_wide = c->ceig_wide;           // last: marks the lists as made for this value
+  return 0;
+}
+
+// The clique step of the wide cliques of an iteration of csp_cone_project_steps, group by group in the one workspace: the
+// launches of ceigw_group with the cone kernels at both ends and its stopping rule without its read-back -- every block
+// sweep the rule allows is enqueued, and the launches behind the check that ended a clique return at their top (section 23).
+// The number of launches depends on the pattern and the tune alone.
+void cone_wide_pass(csp_ctx* c, const MrcArgs& m, hipStream_t st) {
+  DeviceCtx& D = c->D;
+  CeigwArgs a{};
+  a.m = m;
+  a.m.vmode = CW_VMODE_CONE;
+  a.m.w = D.mrc.wbuf;
+  a.vec = 1;
+  a.ws = D.mrc.wws;
+  a.nrun = D.mrc.ints + 2 * c->S.nsn + 3;
+  for (const csp_ctx::ConeGroup& g : c->cone_groups) {
+    a.wd = D.mrc.cone_wdesc + g.first;
+    a.nw = g.nw;
+    const unsigned nw = (unsigned)g.nw, parts = (unsigned)ceigw_parts(g.nfmax);
+    const int steps = g.nbmax + (g.nbmax & 1) - 1;
+    const unsigned tiles = (unsigned)(g.hmax * (g.hmax + 1) / 2 + (int)((g.nfmax + CW_T - 1) / CW_T) * g.hmax);
+    launch(c, KID_ceig, k_ceigw_cone_form, dim3(parts, nw), dim3(MRC_NT), st, a);
+    launch(c, KID_ceig, k_ceigw_begin, dim3(nw), dim3(MRC_NT), st, a);
+    for (int s = 0; s < CEIG_MAX_SWEEPS; ++s) {
+      launch(c, KID_ceig_reduce, k_ceigw_check, dim3(1), dim3(MRC_NT), st, a);
+      for (int r = 0; r < steps; ++r) {
+        launch_lds(c, KID_ceig, k_ceigw_pivot, dim3((unsigned)g.hmax, nw), dim3(MRC_NT), CW_PIVOT_LDS, st, a, r);
+        launch_lds(c, KID_ceig, k_ceigw_apply, dim3(tiles, nw), dim3(MRC_NT), CW_APPLY_LDS, st, a, r, g.hmax);
+      }
+    }
+    launch(c, KID_ceig_reduce, k_ceigw_check, dim3(1), dim3(MRC_NT), st, a);
+    launch(c, KID_ceig, k_ceigw_sort, dim3(nw), dim3(MRC_NT), st, a);
+    launch(c, KID_ceig, k_ceigw_cone_split, dim3(parts, nw), dim3(MRC_NT), st, a);
+    launch(c, KID_ceig, k_ceigw_cone_finish, dim3(nw), dim3(MRC_NT), st, a);
+  }
 }
 
 }  // namespace
@@ -523,8 +606,10 @@ int csp_clique_project(csp_ctx* c, const double* a, double lo, double hi, double
 
 // Iterations it0 .. it0 + nsteps - 1 of the clique-splitting ADMM for the projection of a onto the cone of PSD-completable
 // matrices, on the state (x, U, W) in place.  An iteration: gather_all of x into D.upd, k_cone_split by slot class,
-// k_clique_scatter of W per level into cone_sw (it uses D.upd as its stack, so it comes behind the split), k_cone_update,
-// k_cone_resid into row it of hist.  Nothing is read back and nothing waits (after the first call on the context).
+// the fixed chain of cone_wide_pass for the cliques that CSP_TUNE_CEIG_WIDE sends to the block Jacobi (none at 0),
+// k_clique_scatter of W per level into cone_sw (it uses D.upd as its stack, so it comes behind both), k_cone_update,
+// k_cone_resid into row it of hist.  Nothing is read back, nothing waits, no buffer grows and nothing is uploaded, after
+// the first call on the context under a value of the tune (cone_setup, cone_route).
 int csp_cone_project_steps(csp_ctx* c, const double* a, double* x, double* U, double* W, double rho, double relax, int64_t it0,
                            int64_t nsteps, double* hist, void* stream) {
   if (int rc = ready(c)) return rc;
@@ -536,6 +621,8 @@ int csp_cone_project_steps(csp_ctx* c, const double* a, double* x, double* U, do
   hipStream_t st = (hipStream_t)stream;
   if (int rc = cone_setup(c, st)) return rc;
   if (ranges_overlap({{x, S.blklen()}, {U, c->qlen}, {W, c->qlen}, {hist, 4 * (it0 + nsteps)}}, {{a, S.blklen()}})) return SMCP_EINVAL;
+  if (int rc = cone_route(c, st)) return rc;
+  c->ceig_wide_count = S.nsn - (int64_t)c->cone_need.size();   // the cliques that left the list of k_cone_split
   invalidate_tags(c, x);
   const int64_t nsn = S.nsn;
   const int npart = (int)cone_parts(S);
@@ -548,7 +635,8 @@ int csp_cone_project_steps(csp_ctx* c, const double* a, double* x, double* U, do
   TreeArgs t = tree_args(c);
   for (int64_t it = it0; it < it0 + nsteps; ++it) {
     gather_all(c, x, 0, 1, D.upd, st);
-    if (int rc = mrc_launch<k_cone_split>(c, KID_ceig, m, c->cone_need, 0, nsn, st, D.mrc.cone_list)) return rc;
+    if (int rc = mrc_launch<k_cone_split>(c, KID_ceig, m, c->cone_need, 0, (int64_t)c->cone_need.size(), st, D.mrc.cone_list)) return rc;
+    cone_wide_pass(c, m, st);
     for_levels_up(c, [&](const int32_t* lev, int cnt) {
       t.lev = lev;
       launch(c, KID_gather_level, k_clique_scatter, dim3((unsigned)cnt), dim3(MRC_NT), st, t, (const double*)W, (const int64_t*)D.mrc.qptr,

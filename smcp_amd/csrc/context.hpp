@@ -76,9 +76,11 @@ struct SymmPlan {
 // csp_clique_project that passes no buffer for them (wbuf, rowptr[nsn] doubles); for csp_cone_project_steps, made by its
 // first call (cone_mw marks them as made): the scatter of the W_k and the signed multiplicities (cone_sw, cone_mw, blklen
 // doubles each), per clique the negative eigenvalues and r_k^2 (cone_info, 2 nsn), the partial sums of k_cone_update
-// (cone_part), its own slot-sorted list of all cliques (cone_list) and the most sweeps so far (cone_sweeps, one int); for the
+// (cone_part), its own slot-sorted list of the cliques of k_cone_split (cone_list) and the most sweeps so far (cone_sweeps, one int); for the
 // wide cliques of the clique spectra (front_ceigw.hip, CSP_TUNE_CEIG_WIDE) the workspace of a launch group (wws, wcap
-// doubles) and its descriptors (wdesc, wdesc_cap of them), both grown on demand
+// doubles) and its descriptors (wdesc, wdesc_cap of them), both grown on demand; for the wide cliques of
+// csp_cone_project_steps the descriptors of all its launch groups (cone_wdesc, cone_wdesc_cap of them), which stay on the
+// device from one call to the next (cone_route, completions.hip), in the same workspace wws, and wbuf for their eigenvalues
 struct CeigwDesc;
 struct CompletionWs {
   double* ws = nullptr; int64_t cap = 0;
@@ -88,6 +90,7 @@ struct CompletionWs {
   double* cone_sw = nullptr; double* cone_mw = nullptr; double* cone_info = nullptr; double* cone_part = nullptr;
   int32_t* cone_list = nullptr; int32_t* cone_sweeps = nullptr;
   double* wws = nullptr; int64_t wcap = 0; CeigwDesc* wdesc = nullptr; int64_t wdesc_cap = 0;
+  CeigwDesc* cone_wdesc = nullptr; int64_t cone_wdesc_cap = 0;
 };
 
 // dense PSD completion (front_psd.hip): tile tasks of the fill launches, the columns in level order, and per clique
@@ -367,9 +370,14 @@ struct csp_ctx : smcp::PartitionTables {
   int64_t edm_clamped = 0;              // the same for the last csp_edmcompletion
   int64_t ceig_sweeps = 0;              // the most Jacobi sweeps a clique took in the last csp_clique_eigvalsh / _eigh / _project
   int64_t ceig_wide = 0;                // csp_tune(CSP_TUNE_CEIG_WIDE): the smallest order that takes the block Jacobi of front_ceigw.hip (0: never)
-  int64_t ceig_wide_count = 0;          // cliques that took it in the last csp_clique_eigvalsh / _eigh / _project
+  int64_t ceig_wide_count = 0;          // cliques that took it in the last csp_clique_eigvalsh / _eigh / _project / csp_cone_project_steps
   int64_t qlen = 0;                     // doubles of the packed clique blocks (set with D.mrc.qptr)
   std::vector<int64_t> cone_need;       // slot sizes of the cliques of D.mrc.cone_list, ascending (csp_cone_project_steps)
+  // csp_cone_project_steps under CSP_TUNE_CEIG_WIDE: the value of the tune its lists were made for (-1: not made) and the
+  // launch groups of its wide cliques: descriptors [first, first + nw) of D.mrc.cone_wdesc, with the largest h, nb and nf
+  int64_t cone_wide = -1;
+  struct ConeGroup { int first = 0, nw = 0, hmax = 0, nbmax = 0; int64_t nfmax = 0; };
+  std::vector<ConeGroup> cone_groups;
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
   std::vector<PsdLevel> psd_lev;        // per level with fill work, root first
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy

@@ -31,7 +31,9 @@
 //
 // The projection onto the cone itself (csp_cone_project_steps): k_cone_split, the clique step of a
 // clique-splitting ADMM on top of ceig_jacobi<true>, k_cone_update, the step on the pattern, and k_cone_resid, the row of
-// residuals of an iteration; k_cone_mult makes the multiplicities once per context.  See above each of them.
+// residuals of an iteration; k_cone_mult makes the multiplicities once per context.  See above each of them.  Under
+// CSP_TUNE_CEIG_WIDE the wide cliques leave k_cone_split for the block Jacobi of front_ceigw.hip (k_ceigw_cone_*), which
+// forms T_k by the cone_t below and fills pinfo, rank and flag as k_cone_split does: k_cone_resid sees no difference.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -351,14 +353,20 @@ __global__ void __launch_bounds__(MRC_NT) k_ceig_vec(MrcArgs a) {
 __device__ inline double cone_x(const CliqueDesc& d, const double* P, const double* S, int i, int j) {
   return j < d.nn ? P[i + (int64_t)j * (d.nn + d.na)] : S[(i - d.nn) + (int64_t)(j - d.nn) * d.na];
 }
+// the entry (i >= j, at e = i + j nf) of T_k
+__device__ inline double cone_t(const CliqueDesc& d, const double* P, const double* S, const double* Uk, const double* Wk,
+                                double relax, int i, int j, int e) {
+  const double u = Uk[e], z = Wk[e] + u;
+  return fma(relax, cone_x(d, P, S, i, j) - z, z) + u;
+}
+// workgroup `part` of `nparts` that share the block, as in ceig_form
 __device__ inline void cone_form(const CliqueDesc& d, const double* P, const double* S, const double* Uk, const double* Wk,
-                                 double relax, double* F) {
+                                 double relax, double* F, int part = 0, int nparts = 1) {
   const int nf = d.nn + d.na;
-  for (int e = SMCP_TID; e < nf * nf; e += MRC_NT) {
+  for (int e = part * MRC_NT + SMCP_TID; e < nf * nf; e += nparts * MRC_NT) {
     const int i = e % nf, j = e / nf;
     if (i >= j) {
-      const double u = Uk[e], z = Wk[e] + u;
-      const double v = fma(relax, cone_x(d, P, S, i, j) - z, z) + u;
+      const double v = cone_t(d, P, S, Uk, Wk, relax, i, j, e);
       F[e] = v;
       F[j + (int64_t)i * nf] = v;
     }

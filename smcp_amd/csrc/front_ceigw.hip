@@ -26,6 +26,10 @@
 // projection of k_ceig_vec (vmode 1), entries spread over the workgroups of a launch.
 // Every sum and maximum is a fixed tree or one thread's loop: the same input gives the same bits; the arithmetic on F does
 // not depend on V, so w has the same bits with and without eigenvectors.
+// The clique step of csp_cone_project_steps on the same cliques, at the end of the file:
+// k_ceigw_cone_form (F = T_k) in the place of k_ceigw_form, the kernels above unchanged in a chain of fixed length that the
+// host never looks into, then k_ceigw_sort, k_ceigw_cone_split (U_k and W_k per entry of the lower triangle, the partial
+// sums of r_k^2) and k_ceigw_cone_finish (pinfo, rank, flag) in the place of k_ceigw_out.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -38,7 +42,8 @@ namespace smcp {
 
 constexpr int CW_B = 32, CW_T = 64, CW_LD = 65;       // block width, tile order, leading dimension of a tile in LDS
 constexpr int CW_STATE = 8;                           // status integers per clique (below)
-constexpr int CW_DONE = 0, CW_SWEEPS = 1, CW_NOCONV = 2, CW_NLO = 3, CW_NHI = 4;
+constexpr int CW_DONE = 0, CW_SWEEPS = 1, CW_NOCONV = 2, CW_NLO = 3, CW_NHI = 4, CW_NNEG = 5;
+constexpr int CW_VMODE_CONE = 2;                      // MrcArgs::vmode of the cone pass (k_ceigw_cone_*)
 constexpr size_t CW_APPLY_LDS = (size_t)3 * CW_T * CW_LD * sizeof(double);
 constexpr size_t CW_PIVOT_LDS = (size_t)2 * CW_T * CW_T * sizeof(double);
 
@@ -281,7 +286,8 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_apply(CeigwArgs a, int r, int 
 
 // The end of a clique, one workgroup each: the rank sort of the diagonal into w (and sw, rk, col for k_ceigw_out), with
 // vmode 1 the counts of the eigenvalues outside [lo, hi] and pinfo as k_ceig_vec leaves it; the block sweeps into rank, the
-// status into flag.  A clique that did not converge: NaN in w and pinfo.
+// status into flag.  A clique that did not converge: NaN in w and pinfo.  The cone pass (vmode CW_VMODE_CONE): the number of
+// eigenvalues < 0 into the status words, and pinfo, rank and flag are left to k_ceigw_cone_finish.
 __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
   __shared__ double red[MRC_NT];
   const CeigwDesc w = a.wd[blockIdx.x];
@@ -304,7 +310,12 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
       v.col[rr] = i;
     }
     __syncthreads();
-    if (a.vec && a.m.vmode) {
+    if (a.m.vmode == CW_VMODE_CONE) {
+      double cn = 0.0;
+      for (int rr = SMCP_TID; rr < nf; rr += MRC_NT) cn += v.sw[rr] < 0.0 ? 1.0 : 0.0;
+      const int nneg = (int)ceig_reduce(cn, false, red);
+      if (SMCP_TID == 0) v.state[CW_NNEG] = nneg;
+    } else if (a.vec && a.m.vmode) {
       const double lo = a.m.lo, hi = a.m.hi;
       double cl = 0.0, ch = 0.0, sq = 0.0;
       for (int rr = SMCP_TID; rr < nf; rr += MRC_NT) {
@@ -323,9 +334,9 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
     }
   } else {
     for (int i = SMCP_TID; i < nf; i += MRC_NT) wout[i] = NAN;
-    if (a.vec && a.m.vmode && SMCP_TID == 0) a.m.pinfo[2 * k] = a.m.pinfo[2 * k + 1] = NAN;
+    if (a.vec && a.m.vmode == 1 && SMCP_TID == 0) a.m.pinfo[2 * k] = a.m.pinfo[2 * k + 1] = NAN;
   }
-  if (SMCP_TID == 0) {
+  if (SMCP_TID == 0 && a.m.vmode != CW_VMODE_CONE) {     // (the cone pass: k_ceigw_cone_finish)
     a.m.rank[k] = v.state[CW_SWEEPS];
     a.m.flag[k] = noconv ? CEIG_NO_CONV : 0;
   }
@@ -369,6 +380,93 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_out(CeigwArgs a) {
       Zk[j + (int64_t)i * nf] = z;
     }
   }
+}
+
+// ---- the clique step of csp_cone_project_steps on the wide cliques (k_cone_split of front_ceig.hip, its Jacobi replaced) ----
+// MrcArgs as k_cone_split reads them (Q = U, pw = W, lo = relax, pinfo), vmode = CW_VMODE_CONE, w = a buffer of the context.
+// The chain of an iteration is fixed: k_ceigw_cone_form, k_ceigw_begin, CEIG_MAX_SWEEPS times
+// (k_ceigw_check, the steps of a block sweep), one more k_ceigw_check, k_ceigw_sort, k_ceigw_cone_split, k_ceigw_cone_finish.
+// Nothing looks at the host: the launches behind the check that ended a clique return at their top.
+
+// workgroups of k_ceigw_cone_form / _split that share a clique of order nf, and so the partial sums of its r_k^2: a function
+// of nf alone, whatever else the launch group holds
+__host__ __device__ inline int ceigw_parts(int64_t nf) { return (int)(nf * nf / (MRC_NT * 32) < 1 ? 1 : nf * nf / (MRC_NT * 32) > 64 ? 64 : nf * nf / (MRC_NT * 32)); }
+
+// F = T_k in full (cone_form on the clique's workgroups), V = I
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_cone_form(CeigwArgs a) {
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const int np = ceigw_parts(w.nf);
+  if ((int)blockIdx.x >= np) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  const CliqueDesc d = a.m.cl[w.k];
+  const int64_t q = a.m.qptr[w.k];
+  cone_form(d, a.m.x + d.blk, a.m.upd + d.upd, a.m.Q + q, a.m.pw + q, a.m.lo, v.F, blockIdx.x, np);
+  for (int e = blockIdx.x * MRC_NT + SMCP_TID; e < w.nf * w.nf; e += np * MRC_NT) v.V[e] = (e % (w.nf + 1) == 0) ? 1.0 : 0.0;
+}
+
+// The part of k_cone_split behind its Jacobi.  Every entry i >= j of the lower triangle is one thread's: T_k formed again
+// (the bits of the form step: x, U_k and W_k are as they were), u = the sum over the nneg negative eigenvalues, ascending,
+// with the columns of V taken by rank, then U_k and W_k stored mirrored.  A thread reads U_k and W_k in its own lower-triangle
+// entries only and is the only writer of those and of their mirror images, which nobody reads: no hazard between the
+// workgroups of a launch.  Workgroup p leaves its share of r_k^2 in word p of the clique's U region, which the sweeps are
+// done with.  A clique that did not converge: NaN in U_k and W_k.
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_cone_split(CeigwArgs a) {
+  __shared__ double red[MRC_NT];
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const int nf = w.nf, k = w.k, np = ceigw_parts(nf);
+  if ((int)blockIdx.x >= np) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  const CliqueDesc d = a.m.cl[k];
+  double* Uk = a.m.Q + a.m.qptr[k];
+  double* Wk = a.m.pw + a.m.qptr[k];
+  const int first = blockIdx.x * MRC_NT + SMCP_TID, stride = np * MRC_NT;
+  if (v.state[CW_NOCONV]) {
+    for (int t = first; t < nf * nf; t += stride) Uk[t] = Wk[t] = NAN;
+    return;
+  }
+  const double* P = a.m.x + d.blk;
+  const double* S = a.m.upd + d.upd;
+  const double relax = a.m.lo;
+  const int nneg = v.state[CW_NNEG];
+  double rs = 0.0;
+  for (int t = first; t < nf * nf; t += stride) {
+    const int i = t % nf, j = t / nf;
+    if (i >= j) {
+      double u = 0.0;
+      for (int rr = 0; rr < nneg; ++rr) {
+        const double* q = v.V + (int64_t)v.col[rr] * nf;
+        u += v.sw[rr] * (q[i] * q[j]);
+      }
+      const double tk = cone_t(d, P, S, Uk, Wk, relax, i, j, t), wk = tk - 2.0 * u;
+      const double dz = cone_x(d, P, S, i, j) - (tk - u);
+      rs += i == j ? dz * dz : 2.0 * (dz * dz);
+      Uk[t] = u;
+      Uk[j + (int64_t)i * nf] = u;
+      Wk[t] = wk;
+      Wk[j + (int64_t)i * nf] = wk;
+    }
+  }
+  rs = ceig_reduce(rs, false, red);
+  if (SMCP_TID == 0) v.U[blockIdx.x] = rs;
+}
+
+// One workgroup per clique: pinfo as k_cone_split leaves it (the partial sums of r_k^2 added in index order), the block
+// sweeps into rank, the status into flag; NaN in pinfo for a clique that did not converge.
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_cone_finish(CeigwArgs a) {
+  if (SMCP_TID != 0) return;
+  const CeigwDesc w = a.wd[blockIdx.x];
+  const CeigwView v = ceigw_view(w, a.ws);
+  const int k = w.k, noconv = v.state[CW_NOCONV];
+  if (!noconv) {
+    double rs = 0.0;
+    for (int p = 0; p < ceigw_parts(w.nf); ++p) rs += v.U[p];
+    a.m.pinfo[2 * k] = (double)v.state[CW_NNEG];
+    a.m.pinfo[2 * k + 1] = rs;
+  } else {
+    a.m.pinfo[2 * k] = a.m.pinfo[2 * k + 1] = NAN;
+  }
+  a.m.rank[k] = v.state[CW_SWEEPS];
+  a.m.flag[k] = noconv ? CEIG_NO_CONV : 0;
 }
 
 }  // namespace smcp

@@ -13,6 +13,16 @@ clock around a synchronised call, the two sides alternated, median (min - max) o
 writes as JSON: totals, times per iteration, iteration counts, residuals, and the device time per kernel of one call.
 
     python tools/cone_project_time.py [--reps N] [--maxit N] [--base-iters N] [--out FILE] [case ...]    cases: narrow50k synth50k
+
+With --wide N[,N ...] the tool measures something else: the time per iteration of cone_project under
+tune(symb, TUNE_CEIG_WIDE, N) for every N given (0: the route is off), on a Symbolic per setting, for a chunk of --chunk
+iterations (tol 0: the call runs them all; 3 by default, short enough for a pattern whose iteration takes seconds at 0).
+The settings are alternated inside every repetition; median (min - max) of --reps.  Per setting it also records one
+clique_project(A, 0, inf) on the same context -- the same eigen work with the host-ended block loop; the difference is the
+price of the fixed launch chain -- the most sweeps, the cliques on the route and the device time per kernel of one call.
+The case maxcut is the config-4 max-cut pattern (problems.maxcut_graph_pattern) with the same noisy input.
+
+    python tools/cone_project_time.py --wide 0,65 [--chunk K] [--reps N] [--out FILE] [case ...]    cases: maxcut narrow50k synth50k
 """
 import json
 import math
@@ -97,10 +107,57 @@ def run(name, reps, maxit, base_iters):
     return res
 
 
+WIDE_CASES = dict(CASES, maxcut=CASES["config4"])
+
+
+def run_wide(name, wides, reps, chunk):
+    """per-iteration time of a chunk of cone_project at every setting of TUNE_CEIG_WIDE, one Symbolic per setting"""
+    res = {"case": name, "chunk": chunk, "reps": reps, "rho": RHO, "relax": RELAX, "settings": {}}
+    ctx = {}
+    for wd in wides:
+        symb = WIDE_CASES[name]()
+        symb.device_init(0, 1)
+        chordal.tune(symb, chordal.TUNE_CEIG_WIDE, wd)
+        S = cspmatrix(symb, torch.from_numpy(problems.random_factor_blkval(symb, 1)).cuda())
+        chordal.llt(S)
+        used = chordal.cone_weights(symb) > 0
+        noise = torch.from_numpy(np.random.default_rng(2).standard_normal(symb.blklen)).cuda()
+        A = cspmatrix(symb, torch.where(used, S.blkval + 0.3 * noise, torch.zeros_like(noise)))
+        call = lambda A=A: chordal.cone_project(A, tol=0.0, maxit=chunk, rho=RHO, relax=RELAX, return_info=True)
+        t_first, (X, info) = wall(call)                                # warm: the workspace and the lists of this setting
+        proj = lambda A=A: chordal.clique_project(A, 0.0, math.inf)
+        wall(proj)
+        ctx[wd] = (symb, call, proj, info, t_first)
+    nf = np.diff(ctx[wides[0]][0].rowptr)
+    res.update({"n": ctx[wides[0]][0].n, "nsn": ctx[wides[0]][0].Nsn, "widest_clique": int(nf.max())})
+    t_it = {wd: [] for wd in wides}
+    t_pr = {wd: [] for wd in wides}
+    for _ in range(reps):                                              # alternated
+        for wd in wides:
+            t_it[wd].append(wall(ctx[wd][1])[0] / chunk)
+            t_pr[wd].append(wall(ctx[wd][2])[0])
+    for wd in wides:
+        symb, call, proj, info, t_first = ctx[wd]
+        r = {"first_call_ms": t_first, "per_iteration": stats(t_it[wd]), "clique_project": stats(t_pr[wd]),
+             "chain_price_ms": float(np.median(t_it[wd]) - np.median(t_pr[wd])), "sweeps": info["sweeps"], "wide": info.get("wide", 0),
+             "primal": info["primal"], "dual": info["dual"], "kernels_of_one_call": kernel_ms(symb, call)}
+        res["settings"][str(wd)] = r
+        print("%s wide %d: %.3f ms per iteration (min %.3f max %.3f) over chunks of %d; clique_project %.3f ms (min %.3f max %.3f); "
+              "%d cliques on the route, most sweeps %d; median of %d" % (name, wd, r["per_iteration"]["median_ms"], min(t_it[wd]), max(t_it[wd]),
+                                                                        chunk, r["clique_project"]["median_ms"], min(t_pr[wd]), max(t_pr[wd]),
+                                                                        r["wide"], r["sweeps"], reps), flush=True)
+        print("%s wide %d: kernels of one call: %s" % (name, wd, json.dumps(r["kernels_of_one_call"])), flush=True)
+    return res
+
+
 if __name__ == "__main__":
     args = sys.argv[1:]
-    opts = {"--reps": 5, "--maxit": 300, "--base-iters": 20}
-    out = None
+    opts = {"--reps": 5, "--maxit": 300, "--base-iters": 20, "--chunk": 3}
+    out, wides = None, None
+    if "--wide" in args:
+        i = args.index("--wide")
+        wides = [int(v) for v in args[i + 1].split(",")]
+        del args[i:i + 2]
     for key in list(opts):
         if key in args:
             i = args.index(key)
@@ -113,7 +170,10 @@ if __name__ == "__main__":
     torch.cuda.set_device(0)
     results = []
     for name in (args or ["narrow50k", "synth50k"]):
-        results.append(run(name, opts["--reps"], opts["--maxit"], opts["--base-iters"]))
+        if wides is not None:
+            results.append(run_wide(name, wides, opts["--reps"], opts["--chunk"]))
+        else:
+            results.append(run(name, opts["--reps"], opts["--maxit"], opts["--base-iters"]))
         if out:
             with open(out, "w") as f:
                 json.dump(results, f, indent=1)
