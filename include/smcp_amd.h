@@ -84,8 +84,16 @@ enum {
   CSP_Q_CEIG_SWEEPS = 20, /* 1 value: the most Jacobi sweeps any clique took in the last csp_clique_eigvalsh, csp_clique_eigh or
                              csp_clique_project on this context; for a clique on the wide route (CSP_TUNE_CEIG_WIDE) its BLOCK
                              sweeps are what is counted */
-  CSP_Q_CEIG_WIDE = 21    /* 1 value: the cliques that took the wide route in the last csp_clique_eigvalsh, csp_clique_eigh,
+  CSP_Q_CEIG_WIDE = 21,   /* 1 value: the cliques that took the wide route in the last csp_clique_eigvalsh, csp_clique_eigh,
                              csp_clique_project or csp_cone_project_steps on this context */
+  CSP_Q_SLOT_SHARE = 22,  /* 1 value: the most cliques any one workgroup served from its slot in device memory in the last
+                             completion (rank or factor pass), csp_clique_eigvalsh, csp_clique_eigh, csp_clique_project or
+                             csp_cone_project_steps on this context: ceil(cliques / workgroups) of a launch over slots in
+                             device memory, the largest over the launches of the call; 0: the call made no such launch.  A
+                             host integer: nothing is read back */
+  CSP_Q_CEIG_GROUPS = 23  /* 1 value: the launch groups the wide cliques (CSP_TUNE_CEIG_WIDE) were split into in the last
+                             csp_clique_eigvalsh, csp_clique_eigh, csp_clique_project or csp_cone_project_steps on this context
+                             (CSP_TUNE_SLOT_DOUBLES; 0: no wide clique).  A host integer */
 };
 int64_t csp_symbolic_query(const csp_ctx* ctx, int what, int64_t* out);
 
@@ -633,6 +641,16 @@ int csp_touch(csp_ctx* ctx, const void* ptr);
                                      every call gives the bits it gave before the route existed; with it set, results are
                                      still the same bits from call to call.  Recommended value: 65 (the smallest
                                      scanned value at which the route was not slower than 0 on config 4 and on synth50k) */
+#define CSP_TUNE_SLOT_DOUBLES 8   /* per context: the doubles that the slots in device memory of one launch of the completions and
+                                     clique spectra, or the workspace of one launch group of wide cliques (CSP_TUNE_CEIG_WIDE), may
+                                     take; 0 (default): 2^25, 256 MiB.  Negative: SMCP_EINVAL.  Needs no device; holds from the next
+                                     call on (csp_cone_project_steps builds its lists again and may wait).  A launch always keeps
+                                     one slot and a group one clique, so 1 means one workgroup walking every such clique of a
+                                     launch through one slot, and one wide clique per group.  It exists so that the tests can run
+                                     the slot-sharing loop of those kernels and the group split at small sizes (at the default
+                                     both need about a thousand cliques of more than 126 rows in one launch); a caller may also
+                                     use it to cap workspace memory.  Results do not depend on it, bit for bit; what it changed is
+                                     read with CSP_Q_SLOT_SHARE and CSP_Q_CEIG_GROUPS */
 int csp_tune(csp_ctx* ctx, int what, int64_t value);
 /* out[0], out[1]: milliseconds of the store-pattern probe of the last CSP_TUNE_PLACEMENT before / after (zeros: not run);
  * out[2]: delay kernels injected so far in this process (CSP_TUNE_RACE).  out holds three doubles. */

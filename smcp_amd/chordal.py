@@ -45,6 +45,7 @@ def lazy_status(symb, on=True):
 
 TUNE_LEAFGRAM, TUNE_VERIFY_CACHE, TUNE_DETERMINISTIC, TUNE_PLACEMENT, TUNE_RACE, TUNE_RACE_DROP_JOINS = 1, 2, 3, 4, 5, 6
 TUNE_CEIG_WIDE = 7
+TUNE_SLOT_DOUBLES = 8
 
 
 def tune(symb, what, value):
@@ -61,7 +62,14 @@ def tune(symb, what, value):
     ``clique_project`` diagonalise such cliques by a block Jacobi spread over the whole chip (csrc/front_ceigw.hip) instead of
     one workgroup per clique, and so does every iteration of ``cone_project`` (a fixed chain of launches per iteration, with
     nothing read back; its ``info["wide"]``).  ``max_step`` (the pencil form) ignores it.  ``clique_eig_wide`` tells how
-    many cliques took the route, and ``clique_eig_sweeps`` counts block sweeps for them."""
+    many cliques took the route, and ``clique_eig_sweeps`` counts block sweeps for them.
+
+    TUNE_SLOT_DOUBLES (per Symbolic; value = the doubles that the slots in device memory of one launch of the completions and
+    clique spectra, or the workspace of one launch group of wide cliques, may take; 0 = the default, 2**25; negative values are
+    refused): a launch always keeps one slot and a group one clique, so 1 makes one workgroup walk every clique too wide for
+    LDS through one slot and puts every wide clique into a group of its own.  It is there so that the tests reach those two
+    paths at small sizes, and it caps workspace memory; results do not depend on it, bit for bit.  ``slot_share`` and
+    ``clique_eig_groups`` tell what it did to the last call."""
     _ensure(symb)
     _chk(_lib.lib().csp_tune(symb.handle, int(what), int(value)), "csp_tune")
 
@@ -240,6 +248,25 @@ def clique_eig_wide(symb):
     ``clique_eigh``, ``clique_project`` or ``cone_project`` on symb (CSP_Q_CEIG_WIDE)."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 21, ctypes.byref(out))
+    return out.value
+
+
+def slot_share(symb):
+    """The most cliques any one workgroup served from its slot in device memory in the last completion (either pass),
+    ``clique_eigvalsh``, ``max_step``, ``clique_eigh``, ``clique_project`` or ``cone_project`` chunk on symb: the largest
+    ceil(cliques / workgroups) over the launches of that call that ran from slots in device memory, 0 when there was none
+    (CSP_Q_SLOT_SHARE; above 1 only under ``tune(symb, TUNE_SLOT_DOUBLES, value)`` or with about a thousand such cliques)."""
+    out = ctypes.c_int64(0)
+    _lib.lib().csp_symbolic_query(symb.handle, 22, ctypes.byref(out))
+    return out.value
+
+
+def clique_eig_groups(symb):
+    """The number of launch groups the wide cliques (TUNE_CEIG_WIDE) were split into in the last ``clique_eigvalsh``,
+    ``clique_eigh``, ``clique_project`` or ``cone_project`` chunk on symb (CSP_Q_CEIG_GROUPS): 1 unless their workspace exceeds
+    the limit of TUNE_SLOT_DOUBLES, 0 without a wide clique."""
+    out = ctypes.c_int64(0)
+    _lib.lib().csp_symbolic_query(symb.handle, 23, ctypes.byref(out))
     return out.value
 
 

@@ -2172,6 +2172,12 @@ int64_t csp_symbolic_query(const csp_ctx* c, int what, int64_t* out) {
     case CSP_Q_CEIG_WIDE:
       if (out) out[0] = c->ceig_wide_count;
       return 1;
+    case CSP_Q_SLOT_SHARE:
+      if (out) out[0] = c->slot_share;
+      return 1;
+    case CSP_Q_CEIG_GROUPS:
+      if (out) out[0] = c->ceig_groups;
+      return 1;
   }
   return SMCP_EINVAL;
 }
@@ -2933,6 +2939,10 @@ int csp_tune(csp_ctx* c, int what, int64_t value) {
     case CSP_TUNE_CEIG_WIDE:
       if (value < 0 || (value > 0 && value <= 2 * CW_B)) return SMCP_EINVAL;      // the block Jacobi needs three blocks
       c->ceig_wide = value;
+      return 0;
+    case CSP_TUNE_SLOT_DOUBLES:
+      if (value < 0) return SMCP_EINVAL;
+      c->slot_doubles = value;
       return 0;
     case CSP_TUNE_RACE:
       if (value < 0) return SMCP_EINVAL;

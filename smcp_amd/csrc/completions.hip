@@ -9,6 +9,8 @@ namespace {
 constexpr int64_t MRC_LDS = 128 * 1024;     // bytes of dynamic LDS a slot may take (the rest: the reduction buffers, one
                                             // pair per instantiation of mrc_argmax)
 constexpr int64_t MRC_HBM_DOUBLES = (int64_t)1 << 25;  // HBM slots of one launch: 256 MiB at most (always at least one slot)
+// the same under this context's CSP_TUNE_SLOT_DOUBLES (0: the default above)
+int64_t hbm_doubles(const csp_ctx* c) { return c->slot_doubles > 0 ? c->slot_doubles : MRC_HBM_DOUBLES; }
 
 int mrc_setup(csp_ctx* c) {
   DeviceCtx& D = c->D;
@@ -49,7 +51,8 @@ int mrc_launch(csp_ctx* c, int kid, MrcArgs a, const std::vector<int64_t>& need,
   }
   if (q < e) {
     const int64_t slot = (need[e - 1] + 31) / 32 * 32;
-    const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, MRC_HBM_DOUBLES / slot));
+    const int64_t G = std::min<int64_t>(std::min<int64_t>(e - q, 4 * D.ncu), std::max<int64_t>(1, hbm_doubles(c) / slot));
+    c->slot_share = std::max<int64_t>(c->slot_share, (e - q + G - 1) / G);      // CSP_Q_SLOT_SHARE
     if (int rc = dev_grow(&D.mrc.ws, &D.mrc.cap, G * slot, D.mem, st)) return rc;
     a.lev = list + q;
     a.cnt = (int)(e - q);
@@ -124,6 +127,7 @@ int reduce_flags(csp_ctx* c, int kid, K kern, hipStream_t st, int32_t* out) {
 template <auto Rank, class R>
 int rank_pass(csp_ctx* c, const double* x, double tol, int kid_rank, int kid_reduce, R reduce, bool with_diag, bool out2_is_error,
               int64_t* r, hipStream_t st) {
+  c->slot_share = 0;
   if (int rc = mrc_setup(c)) return rc;
   std::vector<int64_t> need, ranges;
   if (int rc = slot_sorted_lists(c, all_cliques(c->S), [&](int64_t k) { return mrc_slot1(c->S.nf(k)); }, need, ranges, st)) return rc;
@@ -144,6 +148,7 @@ template <auto Factor, class Slot2>
 int factor_pass(csp_ctx* c, const double* x, double tol, int64_t r, double* Y, int64_t ldY, int kid, Slot2 slot2, bool with_diag,
                 int64_t* clamped, hipStream_t st) {
   const Symbolic& S = c->S;
+  c->slot_share = 0;
   if (int rc = mrc_setup(c)) return rc;
   std::vector<int64_t> need, ranges;
   if (int rc = slot_sorted_lists(c, levels_root_first(S), [&](int64_t k) { return slot2(S.nn(k), S.na(k), r); }, need, ranges, st)) return rc;
@@ -280,7 +285,7 @@ int ceigw_group(csp_ctx* c, CeigwArgs a, const std::vector<CeigwDesc>& desc, int
   return 0;
 }
 
-// The wide cliques of a call (ascending), in groups whose workspace stays within MRC_HBM_DOUBLES (always at least one clique)
+// The wide cliques of a call (ascending), in groups whose workspace stays within hbm_doubles (always at least one clique)
 int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
   const Symbolic& S = c->S;
   CeigwArgs a{};
@@ -289,12 +294,14 @@ int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
   std::vector<CeigwDesc> desc;
   int64_t doubles = 0;
   c->ceig_wide_count = 0;
+  c->ceig_groups = 0;
   for (int64_t k = 0; k < S.nsn; ++k) {
     if (!ceig_is_wide(c, k)) continue;
     ++c->ceig_wide_count;
     CeigwDesc w;
     int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, doubles);
-    if (!desc.empty() && doubles + len > MRC_HBM_DOUBLES) {
+    if (!desc.empty() && doubles + len > hbm_doubles(c)) {
+      ++c->ceig_groups;
       if (int rc = ceigw_group(c, a, desc, doubles, st)) return rc;
       desc.clear();
       doubles = 0;
@@ -303,8 +310,9 @@ int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
     desc.push_back(w);
     doubles += len;
   }
-  if (!desc.empty()) return ceigw_group(c, a, desc, doubles, st);
-  return 0;
+  if (desc.empty()) return 0;
+  ++c->ceig_groups;
+  return ceigw_group(c, a, desc, doubles, st);
 }
 
 // csp_clique_eigh (vmode 0) and csp_clique_project (vmode 1): the launches of csp_clique_eigvalsh in standard form with
@@ -314,6 +322,7 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
   const Symbolic& S = c->S;
   DeviceCtx& D = c->D;
   const int64_t nsn = S.nsn;
+  c->slot_share = 0;
   if (int rc = mrc_setup(c)) return rc;
   if (!ext && !D.mrc.ext)
     if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
@@ -375,12 +384,15 @@ int cone_setup(csp_ctx* c, hipStream_t st) {
 // Which clique takes which route in csp_cone_project_steps, made by the first call under a value of CSP_TUNE_CEIG_WIDE and
 // again when a call sees another value (c->cone_wide; it waits for the device and uploads synchronously): the slot-sorted
 // list of the cliques of k_cone_split with its slot sizes -- all cliques at 0, which is the list of a context never tuned --
-// and, for the wide ones, their descriptors (with V) in launch groups within MRC_HBM_DOUBLES, kept on the device, the
-// workspace of the largest group and the buffer of their eigenvalues.  SMCP_EHIP without the 128 KiB LDS class.
+// and, for the wide ones, their descriptors (with V) in launch groups within hbm_doubles, kept on the device, the
+// workspace of the largest group and the buffer of their eigenvalues.  The lists are made again as well when
+// CSP_TUNE_SLOT_DOUBLES has changed (c->cone_limit).  SMCP_EHIP without the 128 KiB LDS class.
 int cone_route(csp_ctx* c, hipStream_t st) {
   const Symbolic& S = c->S;
   DeviceCtx& D = c->D;
-  if (c->cone_wide == c->ceig_wide) return 0;
+  // keyed on both tunes, also at CSP_TUNE_CEIG_WIDE 0, where there are no groups and the lists do not depend on the limit:
+  // one rule, and the remake (with its wait) costs only the call after the limit was changed
+  if (c->cone_wide == c->ceig_wide && c->cone_limit == hbm_doubles(c)) return 0;
   c->cone_wide = -1;
   HIPCHK(hipDeviceSynchronize());        // launches of earlier calls, on whatever stream, may still read the lists
   std::vector<std::pair<int64_t, int32_t>> tmp;
@@ -398,7 +410,7 @@ int cone_route(csp_ctx* c, hipStream_t st) {
     if (!ceig_is_wide(c, k)) continue;
     CeigwDesc w;
     int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), true, doubles);
-    if (c->cone_groups.empty() || (c->cone_groups.back().nw > 0 && doubles + len > MRC_HBM_DOUBLES)) {
+    if (c->cone_groups.empty() || (c->cone_groups.back().nw > 0 && doubles + len > hbm_doubles(c))) {
       csp_ctx::ConeGroup g;
       g.first = (int)desc.size();
       c->cone_groups.push_back(g);
@@ -422,7 +434,8 @@ int cone_route(csp_ctx* c, hipStream_t st) {
     if (!D.mrc.wbuf)
       if (int rc = dev_alloc(&D.mrc.wbuf, S.rowptr[S.nsn], D.mem)) return rc;
   }
-  c->cone_wide = c->ceig_wide;           // last: marks the lists as made for this value
+  c->cone_limit = hbm_doubles(c);
+  c->cone_wide = c->ceig_wide;           // last: marks the lists as made for these values
   return 0;
 }
 
@@ -506,6 +519,7 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
     if (overlap(w, wlen, in, S.blklen()) || overlap(ext, 4, in, S.blklen())) return SMCP_EINVAL;
   if (overlap(w, wlen, ext, 4)) return SMCP_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  c->slot_share = 0;
   if (int rc = mrc_setup(c)) return rc;
   if (b && !D.mrc.upd2)
     if (int rc = dev_alloc(&D.mrc.upd2, S.updlen(), D.mem)) return rc;
@@ -524,6 +538,7 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   m.w = w;
   if (int rc = mrc_launch<k_ceig>(c, KID_ceig, m, need, 0, (int64_t)need.size(), st)) return rc;
   c->ceig_wide_count = 0;
+  c->ceig_groups = 0;
   if (!b)
     if (int rc = ceigw_pass(c, m, false, st)) return rc;
   int32_t* dout = D.mrc.ints + 2 * nsn;
@@ -619,10 +634,12 @@ int csp_cone_project_steps(csp_ctx* c, const double* a, double* x, double* U, do
   const Symbolic& S = c->S;
   DeviceCtx& D = c->D;
   hipStream_t st = (hipStream_t)stream;
+  c->slot_share = 0;
   if (int rc = cone_setup(c, st)) return rc;
   if (ranges_overlap({{x, S.blklen()}, {U, c->qlen}, {W, c->qlen}, {hist, 4 * (it0 + nsteps)}}, {{a, S.blklen()}})) return SMCP_EINVAL;
   if (int rc = cone_route(c, st)) return rc;
   c->ceig_wide_count = S.nsn - (int64_t)c->cone_need.size();   // the cliques that left the list of k_cone_split
+  c->ceig_groups = (int64_t)c->cone_groups.size();
   invalidate_tags(c, x);
   const int64_t nsn = S.nsn;
   const int npart = (int)cone_parts(S);

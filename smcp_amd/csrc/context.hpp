@@ -371,11 +371,15 @@ struct csp_ctx : smcp::PartitionTables {
   int64_t ceig_sweeps = 0;              // the most Jacobi sweeps a clique took in the last csp_clique_eigvalsh / _eigh / _project
   int64_t ceig_wide = 0;                // csp_tune(CSP_TUNE_CEIG_WIDE): the smallest order that takes the block Jacobi of front_ceigw.hip (0: never)
   int64_t ceig_wide_count = 0;          // cliques that took it in the last csp_clique_eigvalsh / _eigh / _project / csp_cone_project_steps
+  int64_t slot_doubles = 0;             // csp_tune(CSP_TUNE_SLOT_DOUBLES): doubles the HBM slots of one launch, or the workspace of one launch group of wide cliques, may take (0: MRC_HBM_DOUBLES)
+  int64_t slot_share = 0;               // CSP_Q_SLOT_SHARE: the most cliques one workgroup served in an HBM-slot launch of the last call (mrc_launch; 0: no such launch)
+  int64_t ceig_groups = 0;              // CSP_Q_CEIG_GROUPS: launch groups of wide cliques in the last csp_clique_eigvalsh / _eigh / _project / csp_cone_project_steps
   int64_t qlen = 0;                     // doubles of the packed clique blocks (set with D.mrc.qptr)
   std::vector<int64_t> cone_need;       // slot sizes of the cliques of D.mrc.cone_list, ascending (csp_cone_project_steps)
   // csp_cone_project_steps under CSP_TUNE_CEIG_WIDE: the value of the tune its lists were made for (-1: not made) and the
   // launch groups of its wide cliques: descriptors [first, first + nw) of D.mrc.cone_wdesc, with the largest h, nb and nf
   int64_t cone_wide = -1;
+  int64_t cone_limit = 0;               // the limit on a group's workspace (hbm_doubles) those groups were made under
   struct ConeGroup { int first = 0, nw = 0, hmax = 0, nbmax = 0; int64_t nfmax = 0; };
   std::vector<ConeGroup> cone_groups;
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2

@@ -89,20 +89,23 @@ def against_the_restatement(name, kind, rho, relax):
         _REF[key] = cone_project_restatement(symb, blk, rho=rho, relax=relax, steps=3, near=bd)
     ref = _REF[key]
     one = three_steps(symb, blk, rho, relax)
-    assert chordal.clique_eig_wide(symb) == n_wide(symb) > 0
-    assert same_bits(one, three_steps(symb, blk, rho, relax, split=True))     # 1 + 2 steps are the 3 of one call
-    assert same_bits(one, three_steps(symb, blk, rho, relax))                 # the same bits from run to run
+    assert chordal.clique_eig_wide(symb) == n_wide(symb) > 0, "%s %s: %d wide cliques taken, %d in the pattern" % (name, kind, chordal.clique_eig_wide(symb), n_wide(symb))
+    assert same_bits(one, three_steps(symb, blk, rho, relax, split=True)), "%s %s: 1 + 2 steps are not the 3 of one call" % (name, kind)
+    assert same_bits(one, three_steps(symb, blk, rho, relax)), "%s %s: two runs differ" % (name, kind)
     a, x, U, W, hist = one
-    assert torch.equal(a.blkval.cpu(), torch.from_numpy(np.array(blk)))       # the input is not written
+    assert torch.equal(a.blkval.cpu(), torch.from_numpy(np.array(blk))), "%s %s: the input was written" % (name, kind)
     xh, Uh, Wh, hh = x.blkval.cpu().numpy(), U.cpu().numpy(), W.cpu().numpy(), hist.cpu().numpy()
     worst = max(np.abs(xh - ref["x"]).max(), np.abs(Uh - ref["U"]).max(), np.abs(Wh - ref["W"]).max()) / unit_of(symb, ref["scale"])
-    assert (xh[~lower_slots(symb)] == 0).all()                                # the unused slots of x
-    for Uk, Wk in zip(unpack(symb, Uh), unpack(symb, Wh)):
-        assert np.array_equal(Uk, Uk.T) and np.array_equal(Wk, Wk.T)          # mirrored on store
-    assert (np.abs(hh[:, 2] - ref["hist"][:, 2]) <= ref["near"]).all()
-    assert (hh[:, 3] == 0).all()
+    tag = "%s %s rho %g relax %g" % (name, kind, rho, relax)
+    assert (xh[~lower_slots(symb)] == 0).all(), "%s: %d unused slots of x are not zero" % (tag, int((xh[~lower_slots(symb)] != 0).sum()))
+    for k, (Uk, Wk) in enumerate(zip(unpack(symb, Uh), unpack(symb, Wh))):     # mirrored on store
+        assert np.array_equal(Uk, Uk.T) and np.array_equal(Wk, Wk.T), "%s: clique %d: |U - U^T| %.3e, |W - W^T| %.3e, bound 0" % (
+            tag, k, np.abs(Uk - Uk.T).max(), np.abs(Wk - Wk.T).max())
+    assert (np.abs(hh[:, 2] - ref["hist"][:, 2]) <= ref["near"]).all(), "%s: negative eigenvalues per iteration %s, restatement %s, allowed difference %s" % (
+        tag, hh[:, 2].tolist(), ref["hist"][:, 2].tolist(), ref["near"].tolist())
+    assert (hh[:, 3] == 0).all(), "%s: cliques that did not converge per iteration %s, bound 0" % (tag, hh[:, 3].tolist())
     if kind == "incone":
-        assert not Uh.any() and (hh[:, 2] == 0).all()
+        assert not Uh.any() and (hh[:, 2] == 0).all(), "%s: max|U| %.3e, negative eigenvalues %s, bound 0" % (tag, np.abs(Uh).max(), hh[:, 2].tolist())
     return worst, hh
 
 
@@ -114,7 +117,7 @@ def test_three_iterations_against_the_restatement(name, kind, rho, relax, capsys
     worst, hh = against_the_restatement(name, kind, rho, relax)
     with capsys.disabled():
         print("\n%s %s rho %g relax %g: %.2f units, hist %s" % (name, kind, rho, relax, worst, hh[-1, :3].tolist()))
-    assert worst <= GPU_FACTOR * CONE_UNITS
+    assert worst <= GPU_FACTOR * CONE_UNITS, "%s %s rho %g relax %g: max error of x, U, W %.3f units, bound %.1f" % (name, kind, rho, relax, worst, GPU_FACTOR * CONE_UNITS)
 
 
 # ---- 2. the contract of the tune -----------------------------------------------------------------------------------------------
@@ -123,35 +126,35 @@ def test_tune_off_and_on_again_on_one_context():
     blk = cone_input(symb, "noisy")
     try:
         first = three_steps(symb, blk, 1.0, 1.7)
-        assert chordal.clique_eig_wide(symb) == 1
+        assert chordal.clique_eig_wide(symb) == 1, "wide cliques taken %d, wanted 1" % chordal.clique_eig_wide(symb)
         chordal.tune(symb, chordal.TUNE_CEIG_WIDE, 0)
         off = three_steps(symb, blk, 1.0, 1.7)
-        assert chordal.clique_eig_wide(symb) == 0
-        assert same_bits(off, three_steps(plain, cone_input(plain, "noisy"), 1.0, 1.7))        # the bits of a context never tuned
-        assert chordal.clique_eig_wide(plain) == 0
+        assert chordal.clique_eig_wide(symb) == 0, "wide cliques taken %d, wanted 0" % chordal.clique_eig_wide(symb)
+        assert same_bits(off, three_steps(plain, cone_input(plain, "noisy"), 1.0, 1.7)), "tune off: not the bits of a context never tuned"        # the bits of a context never tuned
+        assert chordal.clique_eig_wide(plain) == 0, "wide cliques taken on the plain context %d, wanted 0" % chordal.clique_eig_wide(plain)
     finally:
         chordal.tune(symb, chordal.TUNE_CEIG_WIDE, WIDE)
-    assert same_bits(first, three_steps(symb, blk, 1.0, 1.7))                # the bits of the first tuned run
-    assert chordal.clique_eig_wide(symb) == 1
-    assert not same_bits(first, off)                                         # the two routes do differ
+    assert same_bits(first, three_steps(symb, blk, 1.0, 1.7)), "tune on again: not the bits of the first tuned run"                # the bits of the first tuned run
+    assert chordal.clique_eig_wide(symb) == 1, "wide cliques taken %d, wanted 1" % chordal.clique_eig_wide(symb)
+    assert not same_bits(first, off), "the routes at 65 and at 0 gave the same bits"                                         # the two routes do differ
 
 
 def test_no_wide_clique_gives_the_untuned_bits():
     symb, plain = device_symb("band"), device_symb("band", tuned=False)
-    assert n_wide(symb) == 0
+    assert n_wide(symb) == 0, "band has %d wide cliques, wanted 0" % n_wide(symb)
     for kind in ("noisy", "indef"):
-        assert same_bits(three_steps(symb, cone_input(symb, kind), 1.0, 1.7), three_steps(plain, cone_input(plain, kind), 1.0, 1.7))
-        assert chordal.clique_eig_wide(symb) == 0
+        assert same_bits(three_steps(symb, cone_input(symb, kind), 1.0, 1.7), three_steps(plain, cone_input(plain, kind), 1.0, 1.7)), "%s: tuned and plain context differ without a wide clique" % kind
+        assert chordal.clique_eig_wide(symb) == 0, "%s: wide cliques taken %d, wanted 0" % (kind, chordal.clique_eig_wide(symb))
     X, info = chordal.cone_project(on_device(symb, cone_input(symb, "noisy")), return_info=True)
     Xp, infop = chordal.cone_project(on_device(plain, cone_input(plain, "noisy")), return_info=True)
-    assert torch.equal(X.blkval, Xp.blkval) and torch.equal(info["hist"], infop["hist"]) and info["wide"] == infop["wide"] == 0
+    assert torch.equal(X.blkval, Xp.blkval) and torch.equal(info["hist"], infop["hist"]) and info["wide"] == infop["wide"] == 0, "whole call: X or hist differ, wide %s / %s, wanted 0" % (info["wide"], infop["wide"])
 
 
 def test_wide_count_is_reported():
     symb = device_symb("fam_top")
     X, info = chordal.cone_project(on_device(symb, cone_input(symb, "noisy")), maxit=2, return_info=True)
-    assert chordal.clique_eig_wide(symb) == 3 and info["wide"] == 3
-    assert 1 <= info["sweeps"] <= 30
+    assert chordal.clique_eig_wide(symb) == 3 and info["wide"] == 3, "wide cliques %d (query) / %d (info), wanted 3" % (chordal.clique_eig_wide(symb), info["wide"])
+    assert 1 <= info["sweeps"] <= 30, "sweeps %d, bounds 1 and 30" % info["sweeps"]
 
 
 # ---- 3. no data-dependent host loop ----------------------------------------------------------------------------------------------
@@ -164,15 +167,15 @@ def test_launch_chain_does_not_depend_on_the_data():
         run_steps(symb, a, x, U, W, 1.0, 1.7, 0, 1, hist)                     # warm: the lists of this tune
         counts[kind, 1] = launch_counts(symb, lambda: run_steps(symb, a, x, U, W, 1.0, 1.7, 1, 1, hist))
         counts[kind, 2] = launch_counts(symb, lambda: run_steps(symb, a, x, U, W, 1.0, 1.7, 2, 2, hist))
-    assert counts["incone", 1] == counts["indef", 1] and counts["incone", 2] == counts["indef", 2]
-    assert counts["indef", 2] == {k: 2 * v for k, v in counts["indef", 1].items()}
-    assert set(counts["indef", 1]) == {"k_ceig_reduce", "k_axpby", "k_ceig", "k_gather_level"}
+    assert counts["incone", 1] == counts["indef", 1] and counts["incone", 2] == counts["indef", 2], counts
+    assert counts["indef", 2] == {k: 2 * v for k, v in counts["indef", 1].items()}, counts
+    assert set(counts["indef", 1]) == {"k_ceig_reduce", "k_axpby", "k_ceig", "k_gather_level"}, counts["indef", 1]
     # 97 rows: 4 blocks, 3 steps of (pivot, apply) per block sweep; 30 block sweeps, each behind a check, and one check more,
     # then k_cone_resid; under k_ceig: form and begin, the steps, sort, split and finish, and ONE launch of k_cone_split: the
     # two leaves (16 and 18 rows) share the smallest LDS class
-    assert counts["indef", 1]["k_ceig_reduce"] == 31 + 1
-    assert counts["indef", 1]["k_ceig"] == 2 + 30 * 6 + 3 + 1
-    assert counts["indef", 1]["k_axpby"] == 1
+    assert counts["indef", 1]["k_ceig_reduce"] == 31 + 1, counts["indef", 1]
+    assert counts["indef", 1]["k_ceig"] == 2 + 30 * 6 + 3 + 1, counts["indef", 1]
+    assert counts["indef", 1]["k_axpby"] == 1, counts["indef", 1]
 
 
 # ---- 4. the whole call -----------------------------------------------------------------------------------------------------------
@@ -193,11 +196,12 @@ def test_whole_call_against_the_route_at_zero(name, capsys):
         print("\n%s: %d iterations (at 0: %d; warm: %d), primal %.1e dual %.1e, %d wide cliques, %d sweeps at most; |X - X_0| %.2e = %.2f "
               "tol max(1, |A|); min lambda_min %.1e" % (name, info["iterations"], info0["iterations"], info2["iterations"], info["primal"],
                                                          info["dual"], info["wide"], info["sweeps"], diff, diff / (TOL * s), lam))
-    assert info["converged"] and max(info["primal"], info["dual"]) <= TOL and info["wide"] == n_wide(symb) > 0
-    assert info0["converged"] and info0["wide"] == 0
-    assert diff <= 2 * K_BOUND * TOL * s              # each side is within K_BOUND tol scale of the converged projection
-    assert lam >= -info["primal"] * s
-    assert info2["converged"] and info2["iterations"] <= info["iterations"]
+    assert info["converged"] and max(info["primal"], info["dual"]) <= TOL and info["wide"] == n_wide(symb) > 0, "%s: converged %s, primal %.3e dual %.3e (bound %.1e), wide %d of %d" % (name, info["converged"], info["primal"], info["dual"], TOL, info["wide"], n_wide(symb))
+    assert info0["converged"] and info0["wide"] == 0, "%s at 0: converged %s, wide %d (wanted 0)" % (name, info0["converged"], info0["wide"])
+    # each side is within K_BOUND tol scale of the converged projection
+    assert diff <= 2 * K_BOUND * TOL * s, "%s: |X - X_0| %.3e, bound %.3e" % (name, diff, 2 * K_BOUND * TOL * s)
+    assert lam >= -info["primal"] * s, "%s: min lambda_min %.3e, bound %.3e" % (name, lam, -info["primal"] * s)
+    assert info2["converged"] and info2["iterations"] <= info["iterations"], "%s warm start: converged %s, %d iterations, bound %d" % (name, info2["converged"], info2["iterations"], info["iterations"])
 
 
 # ---- 5. the scipy form -------------------------------------------------------------------------------------------------------------
@@ -205,12 +209,13 @@ def test_scipy_form_takes_the_tune():
     symb = device_symb("wide_root70")
     A = sp.csc_matrix(np.tril(dense_of(symb, np.array(cone_input(symb, "noisy")))))
     X, info = smcp_amd.cone_project(A, wide=WIDE, return_info=True)
-    assert info["converged"] and info["wide"] > 0
+    assert info["converged"] and info["wide"] > 0, "scipy form: converged %s, wide %d (wanted > 0)" % (info["converged"], info["wide"])
     X0, info0 = smcp_amd.cone_project(A, wide=0, return_info=True)
     Xn, infon = smcp_amd.cone_project(A, return_info=True)
-    assert info0["wide"] == infon["wide"] == 0 and info0["iterations"] == infon["iterations"]
-    assert np.array_equal(X0.toarray(), Xn.toarray())                        # 0: the bits of the call without the argument
-    assert np.abs(X.toarray() - X0.toarray()).max() <= 2 * K_BOUND * TOL * max(1.0, norm_V(symb, cone_input(symb, "noisy")))
+    assert info0["wide"] == infon["wide"] == 0 and info0["iterations"] == infon["iterations"], "scipy form: wide %d / %d (wanted 0), iterations %d / %d" % (info0["wide"], infon["wide"], info0["iterations"], infon["iterations"])
+    assert np.array_equal(X0.toarray(), Xn.toarray()), "scipy form: wide=0 differs from the call without the argument by %.3e, bound 0" % np.abs(X0.toarray() - Xn.toarray()).max()                        # 0: the bits of the call without the argument
+    bd = 2 * K_BOUND * TOL * max(1.0, norm_V(symb, cone_input(symb, "noisy")))
+    assert np.abs(X.toarray() - X0.toarray()).max() <= bd, "scipy form: |X - X_0| %.3e, bound %.3e" % (np.abs(X.toarray() - X0.toarray()).max(), bd)
     for bad in (10, 1, 64, -1):
         with pytest.raises(ValueError):
             smcp_amd.cone_project(A, wide=bad)
@@ -224,9 +229,9 @@ def test_non_finite_entry_names_the_wide_clique_at_the_first_look():
     bad[symb.blkptr[kr] + 50 + 40 * 70] = np.nan                              # row 50, column 40 of the root: in no separator
     with pytest.raises(RuntimeError, match="did not converge") as e:
         chordal.cone_project(on_device(symb, bad))
-    assert int(str(e.value).split("clique ")[1].split()[0]) == kr and "at iteration 1 " in str(e.value)
+    assert int(str(e.value).split("clique ")[1].split()[0]) == kr and "at iteration 1 " in str(e.value), (str(e.value), kr)
     X, info = chordal.cone_project(on_device(symb, cone_input(symb, "noisy")), return_info=True)
-    assert info["converged"] and info["wide"] == 1                           # nothing is left behind for the next call
+    assert info["converged"] and info["wide"] == 1, "after the NaN: converged %s, wide %d (wanted 1)" % (info["converged"], info["wide"])                           # nothing is left behind for the next call
 
 
 # ---- 7. poison run -----------------------------------------------------------------------------------------------------------------
@@ -238,7 +243,7 @@ def poison_line(name, kind, fresh):
     if fresh:
         _SYMB.pop((name, True), None)
     worst, hh = against_the_restatement(name, kind, *PARAMS[0])
-    assert worst <= GPU_FACTOR * CONE_UNITS
+    assert worst <= GPU_FACTOR * CONE_UNITS, "poisoned %s %s: %.3f units, bound %.1f" % (name, kind, worst, GPU_FACTOR * CONE_UNITS)
     return "poisoned workspace %s %s: %.2f units" % (name, kind, worst)
 
 
