@@ -262,8 +262,10 @@ int csp_psdcompletion(csp_ctx* ctx, const double* blkval, double tol, double* Xd
  * smallest eigenvalue over all cliques, the lowest clique attaining it, the largest, and the lowest clique attaining that.
  * One workgroup per clique: a Cholesky of B_gg and two triangular solves (pencil form), a two-sided cyclic Jacobi in a
  * fixed parallel order without eigenvectors, a rank sort; at most six launches plus one whatever the tree, beside the
- * top-down gathers of the separator blocks (in standard form under CSP_TUNE_CEIG_WIDE the wide cliques leave these launches
- * for a block Jacobi over the whole chip: two launches per step of a block sweep, one integer read back per block sweep).
+ * top-down gathers of the separator blocks (under CSP_TUNE_CEIG_WIDE the wide cliques leave these launches, in both forms,
+ * for a block Jacobi over the whole chip: two launches per step of a block sweep, one integer read back per block sweep; in
+ * pencil form the Cholesky of B_gg and the two solves run in front of it by 64-row tiles over the chip, 3 ceil(nf / 64) + 1
+ * launches for the widest clique whatever the data, and a B_gg that is not positive definite is reported as without the tune).
  * The same input gives the same bits.  Returns 0, 1 + k when B_gg of clique k
  * is not positive definite, SMCP_ENOCONV when a clique did not converge in 30 sweeps (a non-finite entry ends this way),
  * SMCP_EINVAL for a null a or w, a replicated context, or w / ext overlapping a, b or each other.  The most sweeps of a
@@ -630,14 +632,15 @@ int csp_touch(csp_ctx* ctx, const void* ptr);
                                      recorded, the caller's stream does not wait for it): results are WRONG by design and must
                                      change under CSP_TUNE_RACE, which is what tests/test_gpu_parity.py asserts.  0: back to normal
                                      (waits for the device).  PROCESS-wide. */
-#define CSP_TUNE_CEIG_WIDE 7      /* per context: the smallest order of a clique whose spectrum in standard form
-                                     (csp_clique_eigvalsh without b, csp_clique_eigh, csp_clique_project) is computed by the
+#define CSP_TUNE_CEIG_WIDE 7      /* per context: the smallest order of a clique whose spectrum (csp_clique_eigvalsh with
+                                     and without b, csp_clique_eigh, csp_clique_project) is computed by the
                                      chip-wide block Jacobi of front_ceigw.hip (pivots of two 32-column blocks on one workgroup
                                      each, 64 x 64 tile products on the matrix cores over all compute units) instead of one
                                      workgroup per clique; 0 (default): never.  1 .. 64 and negative values: SMCP_EINVAL (the
                                      route needs three blocks).  csp_cone_project_steps sends the same cliques through it in
                                      every iteration, by a fixed chain of launches that reads nothing back; the first call
-                                     after the value changed builds its lists again and may wait.  The pencil form ignores it.  With 0
+                                     after the value changed builds its lists again and may wait.  The pencil form (b given) reduces (A_gg, B_gg) to standard
+                                     form by tiles over the chip first.  With 0
                                      every call gives the bits it gave before the route existed; with it set, results are
                                      still the same bits from call to call.  Recommended value: 65 (the smallest
                                      scanned value at which the route was not slower than 0 on config 4 and on synth50k) */

@@ -575,12 +575,20 @@ def cone_project(A, cone="primal", tol=1e-8, maxit=500, rho=1.0, relax=1.7, retu
     return out[0].spmatrix(reordered=False, symmetric=True), info
 
 
-def max_step(X, D):
+def max_step(X, D, wide=0):
     """sup{alpha >= 0 : X + alpha D has a positive definite completion} for sparse symmetric X, D (scipy sparse, either
     triangle or both) whose joint pattern is chordal and X inside the cone; math.inf when no step leaves it
-    (smcp_amd.chordal.max_step).  ValueError for a pattern that is not chordal, ArithmeticError for X outside the cone."""
+    (smcp_amd.chordal.max_step).  wide: the smallest order of a clique whose pencil runs on the whole chip
+    (``chordal.tune(symb, TUNE_CEIG_WIDE, wide)`` on the Symbolic this call builds, as in ``cone_project``); 0, the default,
+    sends none there.  ValueError for a pattern that is not chordal and for a `wide` in 1 .. 64 or below 0, ArithmeticError
+    for X outside the cone."""
     from . import chordal
+    wide = int(wide)
+    if wide < 0 or 1 <= wide <= 64:
+        raise ValueError("max_step: wide must be 0 or at least 65")
     Xc, Dc = _on_chordal_pattern([X, D], "max_step")
+    if wide:                                    # (0: the default path as it was, the Symbolic is new and its tune is 0)
+        chordal.tune(Xc.symb, chordal.TUNE_CEIG_WIDE, wide)
     return chordal.max_step(Xc, Dc)
 
 

@@ -58,10 +58,11 @@ def tune(symb, what, value):
     0 = off, process-wide: seeded delay injection on every internal stream hand-over, tools/race_hunt.sh).
 
     TUNE_CEIG_WIDE (per Symbolic; value = the smallest order of a clique that takes the wide route, 0 = never, the default;
-    1 .. 64 and negative values are refused: RuntimeError, invalid argument): ``clique_eigvalsh`` without B, ``cone_margin``, ``clique_eigh`` and
-    ``clique_project`` diagonalise such cliques by a block Jacobi spread over the whole chip (csrc/front_ceigw.hip) instead of
+    1 .. 64 and negative values are refused: RuntimeError, invalid argument): ``clique_eigvalsh`` (with and without B), ``cone_margin``, ``max_step``,
+    ``clique_eigh`` and ``clique_project`` diagonalise such cliques by a block Jacobi spread over the whole chip (csrc/front_ceigw.hip) instead of
     one workgroup per clique, and so does every iteration of ``cone_project`` (a fixed chain of launches per iteration, with
-    nothing read back; its ``info["wide"]``).  ``max_step`` (the pencil form) ignores it.  ``clique_eig_wide`` tells how
+    nothing read back; its ``info["wide"]``).  With B given (``max_step``) the Cholesky of B_gg and the two triangular solves run
+    by 64-row tiles over the chip in front of the block Jacobi.  ``clique_eig_wide`` tells how
     many cliques took the route, and ``clique_eig_sweeps`` counts block sweeps for them.
 
     TUNE_SLOT_DOUBLES (per Symbolic; value = the doubles that the slots in device memory of one launch of the completions and
@@ -225,7 +226,10 @@ def clique_eigvalsh(A, B=None):
     (A_gg, B_gg), that is of B_gg^-1 A_gg.  A and B are cspmatrices on the same Symbolic (ValueError otherwise) read as
     symmetric matrices (of a supernode's diagonal block the lower triangle counts, as ``symm`` reads it); neither is written.
     ArithmeticError naming the clique when a B_gg is not positive definite, RuntimeError when a clique did not converge in
-    30 Jacobi sweeps (a non-finite entry ends this way).  The same input gives the same bits (csp_clique_eigvalsh)."""
+    30 Jacobi sweeps (a non-finite entry ends this way).  The same input gives the same bits (csp_clique_eigvalsh).
+    A clique wider than 89 rows (126 without B) runs on one workgroup from device memory and is slow, unless
+    ``tune(symb, TUNE_CEIG_WIDE, 65)`` sends it through the chip-wide route, which both forms take; errors and the clique they
+    name are the same either way."""
     return _clique_eig(A, B, "clique_eigvalsh")[0]
 
 
@@ -244,8 +248,9 @@ def clique_eig_sweeps(symb):
 
 
 def clique_eig_wide(symb):
-    """The number of cliques that took the wide route (``tune(symb, TUNE_CEIG_WIDE, order)``) in the last ``clique_eigvalsh``,
-    ``clique_eigh``, ``clique_project`` or ``cone_project`` on symb (CSP_Q_CEIG_WIDE)."""
+    """The number of cliques that took the wide route (``tune(symb, TUNE_CEIG_WIDE, order)``) in the last ``clique_eigvalsh``
+    (with or without B, so ``clique_extremes``, ``cone_margin`` and ``max_step`` as well), ``clique_eigh``, ``clique_project`` or
+    ``cone_project`` on symb (CSP_Q_CEIG_WIDE)."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 21, ctypes.byref(out))
     return out.value
@@ -262,9 +267,10 @@ def slot_share(symb):
 
 
 def clique_eig_groups(symb):
-    """The number of launch groups the wide cliques (TUNE_CEIG_WIDE) were split into in the last ``clique_eigvalsh``,
-    ``clique_eigh``, ``clique_project`` or ``cone_project`` chunk on symb (CSP_Q_CEIG_GROUPS): 1 unless their workspace exceeds
-    the limit of TUNE_SLOT_DOUBLES, 0 without a wide clique."""
+    """The number of launch groups the wide cliques (TUNE_CEIG_WIDE) were split into in the last ``clique_eigvalsh`` (with or
+    without B, so ``max_step`` as well; with B a clique's workspace holds B_gg too), ``clique_eigh``, ``clique_project`` or
+    ``cone_project`` chunk on symb (CSP_Q_CEIG_GROUPS): 1 unless their workspace exceeds the limit of TUNE_SLOT_DOUBLES, 0
+    without a wide clique."""
     out = ctypes.c_int64(0)
     _lib.lib().csp_symbolic_query(symb.handle, 23, ctypes.byref(out))
     return out.value
@@ -283,7 +289,8 @@ def max_step(X, D, return_clique=False):
     pencils (D_gg, X_gg) it is -1 / mu for mu < 0 and math.inf otherwise.  return_clique=True: (alpha, clique) with the
     binding clique (the one whose block of X + alpha D is singular; the clique of mu when alpha is inf).  ArithmeticError
     naming the clique when X is outside the cone (the Cholesky of X_gg inside the pencil), ValueError for different
-    Symbolics.  One ``clique_eigvalsh``: no trial factorisation."""
+    Symbolics.  One ``clique_eigvalsh``: no trial factorisation.  Under ``tune(symb, TUNE_CEIG_WIDE, 65)`` the wide cliques
+    take the chip-wide route (the pencil form of it), which is what makes the call usable on a root of several hundred rows."""
     import math
     e = _clique_eig(D, X, "max_step")[1].cpu()
     mu = float(e[0])

@@ -250,9 +250,14 @@ bool ceig_is_wide(const csp_ctx* c, int64_t k) { return c->ceig_wide > 0 && c->S
 
 // One launch group of wide cliques: form, then block sweeps until no clique of the group runs (one integer read back per
 // sweep), then the rank sort and the output blocks.  m.rank / m.flag of these cliques are filled as k_ceig fills them.
+// Pencil mode (a.pencil): behind the form the reduction to standard form, 3 ntmax + 1 launches for the most 64-row tiles
+// ntmax of a clique of the group (front_ceigw.hip), whatever the data.
 int ceigw_group(csp_ctx* c, CeigwArgs a, const std::vector<CeigwDesc>& desc, int64_t doubles, hipStream_t st) {
   DeviceCtx& D = c->D;
   if (lds_ceiling<k_ceigw_pivot>() < (int64_t)CW_PIVOT_LDS + 4096 || lds_ceiling<k_ceigw_apply>() < (int64_t)CW_APPLY_LDS + 4096) return SMCP_EHIP;
+  if (a.pencil && (lds_ceiling<k_ceigw_panel>() < (int64_t)CW_APPLY_LDS + 4096 || lds_ceiling<k_ceigw_trail>() < (int64_t)CW_APPLY_LDS + 4096 ||
+                   lds_ceiling<k_ceigw_solve<true>>() < (int64_t)CW_APPLY_LDS + 4096 || lds_ceiling<k_ceigw_solve<false>>() < (int64_t)CW_APPLY_LDS + 4096))
+    return SMCP_EHIP;
   const int nw = (int)desc.size();
   if (int rc = dev_grow(&D.mrc.wws, &D.mrc.wcap, doubles, D.mem, st)) return rc;
   if (int rc = dev_grow(&D.mrc.wdesc, &D.mrc.wdesc_cap, (int64_t)nw, D.mem, st)) return rc;
@@ -268,6 +273,20 @@ int ceigw_group(csp_ctx* c, CeigwArgs a, const std::vector<CeigwDesc>& desc, int
   const unsigned parts = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, nfmax * nfmax / (MRC_NT * 32)));
   const unsigned tiles = (unsigned)(hmax * (hmax + 1) / 2 + (a.vec ? (int)((nfmax + CW_T - 1) / CW_T) * hmax : 0));
   launch(c, KID_ceig, k_ceigw_form, dim3(parts, (unsigned)nw), dim3(MRC_NT), st, a);
+  if (a.pencil) {
+    const int ntmax = (int)((nfmax + CW_T - 1) / CW_T);
+    const size_t tile = (size_t)CW_T * CW_LD * sizeof(double);
+    for (int j = 0; j < ntmax; ++j) {
+      launch_lds(c, KID_ceig, k_ceigw_potrf, dim3((unsigned)nw), dim3(MRC_NT), tile, st, a, j);
+      const unsigned rem = (unsigned)(ntmax - 1 - j);
+      if (rem == 0) break;
+      launch_lds(c, KID_ceig, k_ceigw_panel, dim3(rem, (unsigned)nw), dim3(MRC_NT), 2 * tile, st, a, j);
+      launch_lds(c, KID_ceig, k_ceigw_trail, dim3(rem * (rem + 1) / 2, (unsigned)nw), dim3(MRC_NT), 2 * tile, st, a, j);
+    }
+    launch_lds(c, KID_ceig, k_ceigw_solve<true>, dim3((unsigned)ntmax, (unsigned)nw), dim3(MRC_NT), CW_APPLY_LDS, st, a);
+    launch_lds(c, KID_ceig, k_ceigw_solve<false>, dim3((unsigned)ntmax, (unsigned)nw), dim3(MRC_NT), CW_APPLY_LDS, st, a);
+    launch(c, KID_ceig, k_ceigw_symm, dim3(parts, (unsigned)nw), dim3(MRC_NT), st, a);
+  }
   launch(c, KID_ceig, k_ceigw_begin, dim3((unsigned)nw), dim3(MRC_NT), st, a);
   for (;;) {
     launch(c, KID_ceig_reduce, k_ceigw_check, dim3(1), dim3(MRC_NT), st, a);
@@ -285,12 +304,14 @@ int ceigw_group(csp_ctx* c, CeigwArgs a, const std::vector<CeigwDesc>& desc, int
   return 0;
 }
 
-// The wide cliques of a call (ascending), in groups whose workspace stays within hbm_doubles (always at least one clique)
-int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
+// The wide cliques of a call (ascending), in groups whose workspace stays within hbm_doubles (always at least one clique);
+// pencil: m.x2 / m.upd2 hold B, and the workspace of a clique holds G as well
+int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, bool pencil, hipStream_t st) {
   const Symbolic& S = c->S;
   CeigwArgs a{};
   a.m = m;
   a.vec = vec ? 1 : 0;
+  a.pencil = pencil ? 1 : 0;
   std::vector<CeigwDesc> desc;
   int64_t doubles = 0;
   c->ceig_wide_count = 0;
@@ -299,13 +320,13 @@ int ceigw_pass(csp_ctx* c, const MrcArgs& m, bool vec, hipStream_t st) {
     if (!ceig_is_wide(c, k)) continue;
     ++c->ceig_wide_count;
     CeigwDesc w;
-    int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, doubles);
+    int64_t len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, doubles, pencil);
     if (!desc.empty() && doubles + len > hbm_doubles(c)) {
       ++c->ceig_groups;
       if (int rc = ceigw_group(c, a, desc, doubles, st)) return rc;
       desc.clear();
       doubles = 0;
-      len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, 0);
+      len = ceigw_layout(w, (int32_t)k, S.nf(k), vec, 0, pencil);
     }
     desc.push_back(w);
     doubles += len;
@@ -339,7 +360,7 @@ int ceig_vec_pass(csp_ctx* c, const double* a, int vmode, double lo, double hi, 
   m.pinfo = info;
   m.vmode = vmode;
   if (int rc = mrc_launch<k_ceig_vec>(c, KID_ceig, m, need, 0, (int64_t)need.size(), st)) return rc;
-  if (int rc = ceigw_pass(c, m, true, st)) return rc;
+  if (int rc = ceigw_pass(c, m, true, false, st)) return rc;
   int32_t* dout = D.mrc.ints + 2 * nsn;
   launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
          (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);
@@ -507,7 +528,8 @@ int csp_maxcut_cuts(csp_ctx* c, const double* Y, int64_t ldY, int64_t r, int64_t
 
 // ---- spectra of the clique blocks (front_ceig.hip) ------------------------------------------------------------------
 // One launch group over all cliques, as pass 1 of the completions: the separator blocks of A (and of B, into the second
-// gather buffer) gathered top-down, k_ceig by slot size, k_ceig_reduce, and the read-back of its three integers.
+// gather buffer) gathered top-down, k_ceig by slot size, the wide cliques of CSP_TUNE_CEIG_WIDE in ceigw_pass (standard
+// and pencil form), k_ceig_reduce, and the read-back of its three integers.
 int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w, double* ext, void* stream) {
   if (int rc = ready(c)) return rc;
   if (!a || !w || c->ntrial != 1) return SMCP_EINVAL;
@@ -526,8 +548,8 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   if (!ext && !D.mrc.ext)
     if (int rc = dev_alloc(&D.mrc.ext, 4, D.mem)) return rc;
   std::vector<int64_t> need, ranges;
-  // the wide cliques of the standard form leave the list for the block Jacobi of front_ceigw.hip (the pencil form ignores the tune)
-  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return b ? ceig_slot2(S.nf(k)) : ceig_is_wide(c, k) ? (int64_t)-1 : ceig_slot1(S.nf(k)); },
+  // the wide cliques leave the list for the block Jacobi of front_ceigw.hip, in both forms
+  if (int rc = slot_sorted_lists(c, all_cliques(S), [&](int64_t k) { return ceig_is_wide(c, k) ? (int64_t)-1 : b ? ceig_slot2(S.nf(k)) : ceig_slot1(S.nf(k)); },
                                  need, ranges, st))
     return rc;
   gather_all(c, a, 0, 1, D.upd, st);
@@ -537,10 +559,7 @@ int csp_clique_eigvalsh(csp_ctx* c, const double* a, const double* b, double* w,
   m.upd2 = D.mrc.upd2;
   m.w = w;
   if (int rc = mrc_launch<k_ceig>(c, KID_ceig, m, need, 0, (int64_t)need.size(), st)) return rc;
-  c->ceig_wide_count = 0;
-  c->ceig_groups = 0;
-  if (!b)
-    if (int rc = ceigw_pass(c, m, false, st)) return rc;
+  if (int rc = ceigw_pass(c, m, false, b != nullptr, st)) return rc;
   int32_t* dout = D.mrc.ints + 2 * nsn;
   launch(c, KID_ceig_reduce, k_ceig_reduce, dim3(1), dim3(MRC_NT), st, (const CliqueDesc*)D.cl, (const double*)w, (const int32_t*)m.rank,
          (const int32_t*)m.flag, (int)nsn, ext ? ext : D.mrc.ext, dout);

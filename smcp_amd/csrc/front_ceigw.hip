@@ -26,6 +26,9 @@
 // projection of k_ceig_vec (vmode 1), entries spread over the workgroups of a launch.
 // Every sum and maximum is a fixed tree or one thread's loop: the same input gives the same bits; the arithmetic on F does
 // not depend on V, so w has the same bits with and without eigenvectors.
+// The pencil form (csp_clique_eigvalsh with b): G = B_gg beside F, and between k_ceigw_form and
+// k_ceigw_begin the reduction F <- R^-1 F R^-T, G = R R^T, on tiles of CW_T rows (k_ceigw_potrf / _panel / _trail / _solve /
+// _symm, described where they stand); the chain above then runs unchanged.
 // The clique step of csp_cone_project_steps on the same cliques, at the end of the file:
 // k_ceigw_cone_form (F = T_k) in the place of k_ceigw_form, the kernels above unchanged in a chain of fixed length that the
 // host never looks into, then k_ceigw_sort, k_ceigw_cone_split (U_k and W_k per entry of the lower triangle, the partial
@@ -43,17 +46,20 @@ namespace smcp {
 constexpr int CW_B = 32, CW_T = 64, CW_LD = 65;       // block width, tile order, leading dimension of a tile in LDS
 constexpr int CW_STATE = 8;                           // status integers per clique (below)
 constexpr int CW_DONE = 0, CW_SWEEPS = 1, CW_NOCONV = 2, CW_NLO = 3, CW_NHI = 4, CW_NNEG = 5;
+constexpr int CW_NOTPD = 6;                           // pencil mode: a diagonal tile of B_gg met a pivot that is not > 0
 constexpr int CW_VMODE_CONE = 2;                      // MrcArgs::vmode of the cone pass (k_ceigw_cone_*)
 constexpr size_t CW_APPLY_LDS = (size_t)3 * CW_T * CW_LD * sizeof(double);
 constexpr size_t CW_PIVOT_LDS = (size_t)2 * CW_T * CW_T * sizeof(double);
 
 // One wide clique of a call: offsets in doubles into the workspace.  h: pairs of a step.  V: -1 without eigenvectors.
+// G: B_gg in full and then its Cholesky factor (pencil mode), -1 in standard form.
 struct CeigwDesc {
   int32_t k, nf, nb, h;
-  int64_t F, V, U, ev, slot, sw, st, ints;
+  int64_t F, V, U, ev, slot, sw, st, ints, G;
 };
-// doubles of the workspace of one clique and its layout from `base` on
-__host__ inline int64_t ceigw_layout(CeigwDesc& w, int32_t k, int64_t nf, bool vec, int64_t base) {
+// doubles of the workspace of one clique and its layout from `base` on; pencil: room for G behind V (no other offset moves
+// without it)
+__host__ inline int64_t ceigw_layout(CeigwDesc& w, int32_t k, int64_t nf, bool vec, int64_t base, bool pencil = false) {
   w.k = k;
   w.nf = (int32_t)nf;
   w.nb = (int32_t)((nf + CW_B - 1) / CW_B);
@@ -61,6 +67,7 @@ __host__ inline int64_t ceigw_layout(CeigwDesc& w, int32_t k, int64_t nf, bool v
   int64_t o = base;
   w.F = o; o += nf * nf;
   w.V = vec ? o : -1; o += vec ? nf * nf : 0;
+  w.G = pencil ? o : -1; o += pencil ? nf * nf : 0;
   w.U = o; o += (int64_t)w.h * CW_T * CW_T;
   w.ev = o; o += (int64_t)w.h * CW_T;                  // (>= nf doubles: k_ceigw_sort keeps the diagonal here)
   w.slot = o; o += (int64_t)w.h * (w.h + 1) / 2;
@@ -71,25 +78,27 @@ __host__ inline int64_t ceigw_layout(CeigwDesc& w, int32_t k, int64_t nf, bool v
 }
 
 struct CeigwView {
-  double *F, *V, *U, *ev, *slot, *sw, *st;
+  double *F, *V, *G, *U, *ev, *slot, *sw, *st;
   int32_t *rk, *col, *uflag, *state;
 };
 __device__ inline CeigwView ceigw_view(const CeigwDesc& w, double* ws) {
   CeigwView v;
-  v.F = ws + w.F; v.V = w.V >= 0 ? ws + w.V : nullptr; v.U = ws + w.U; v.ev = ws + w.ev; v.slot = ws + w.slot;
+  v.F = ws + w.F; v.V = w.V >= 0 ? ws + w.V : nullptr; v.G = w.G >= 0 ? ws + w.G : nullptr; v.U = ws + w.U; v.ev = ws + w.ev; v.slot = ws + w.slot;
   v.sw = ws + w.sw; v.st = ws + w.st;
   v.rk = (int32_t*)(ws + w.ints); v.col = v.rk + w.nf; v.uflag = v.col + w.nf; v.state = v.uflag + w.h;
   return v;
 }
 
 // MrcArgs m as k_ceig_vec reads them (standard form); wd / nw: the wide cliques of this launch group, ws: their workspace,
-// vec: eigenvectors are accumulated; nrun: the cliques still running (k_ceigw_check)
+// vec: eigenvectors are accumulated; nrun: the cliques still running (k_ceigw_check); pencil: m.x2 / m.upd2 hold B and the
+// reduction to standard form runs between k_ceigw_form and k_ceigw_begin
 struct CeigwArgs {
   MrcArgs m;
   const CeigwDesc* wd;
   double* ws;
   int nw, vec;
   int32_t* nrun;
+  int pencil;
 };
 
 // pair t of step r on the nb blocks of a clique of order nf: rows r0 .. r0 + n0 of block I, then r1 .. r1 + n1 of block J
@@ -107,18 +116,167 @@ __device__ inline int ceigw_row(const CeigwPair& P, int a) { return a < P.n0 ? P
 
 __device__ inline double ceigw_nanmax(double x, double y) { return (y > x || y != y) ? y : x; }
 
-// F = A_gg in full (ceig_form on gridDim.x workgroups per clique), V = I
+// F = A_gg in full (ceig_form on gridDim.x workgroups per clique), V = I; pencil mode: G = B_gg in full as well, and the two
+// status words that the reduction reads before k_ceigw_begin has run
 __global__ void __launch_bounds__(MRC_NT) k_ceigw_form(CeigwArgs a) {
   const CeigwDesc w = a.wd[blockIdx.y];
   const CeigwView v = ceigw_view(w, a.ws);
   const CliqueDesc d = a.m.cl[w.k];
   ceig_form(d, a.m.x + d.blk, a.m.upd + d.upd, v.F, blockIdx.x, gridDim.x);
+  if (a.pencil) {
+    ceig_form(d, a.m.x2 + d.blk, a.m.upd2 + d.upd, v.G, blockIdx.x, gridDim.x);
+    if (blockIdx.x == 0 && SMCP_TID == 0) v.state[CW_DONE] = v.state[CW_NOTPD] = 0;
+  }
   if (a.vec)
     for (int e = blockIdx.x * MRC_NT + SMCP_TID; e < w.nf * w.nf; e += gridDim.x * MRC_NT) v.V[e] = (e % (w.nf + 1) == 0) ? 1.0 : 0.0;
 }
 
+// ---- pencil mode: F <- R^-1 F R^-T with G = R R^T, between k_ceigw_form and k_ceigw_begin ----------
+// Tiles of CW_T rows: nt = ceil(nf / CW_T), the last one may be a single row.  Only the tiles (i, l), i >= l, of G are kept
+// up: they end as R (a diagonal tile with zeros above its diagonal); the tiles above stay B_gg and nobody reads them.
+// The launches, for the most tiles ntmax of a group: per block column j a k_ceigw_potrf (the diagonal tile), and for
+// j < ntmax - 1 a k_ceigw_panel (the tiles below it) and a k_ceigw_trail (the tiles right of the panel); then k_ceigw_lsolve,
+// k_ceigw_rsolve, k_ceigw_symm: 3 ntmax + 1, whatever the data.  Every tile written in a launch has one owner, which reads
+// beside it only what earlier launches wrote, or (the slab solves) what it wrote itself.  No atomics, no waits.
+// A pivot that is not > 0 (a NaN is not): k_ceigw_potrf raises CW_NOTPD and CW_DONE, and every later launch of the chain
+// returns at its top for that clique.
+__device__ inline int ceigw_tn(int nf, int t) { return min(CW_T, nf - t * CW_T); }
+__device__ inline int ceigw_nt(int nf) { return (nf + CW_T - 1) / CW_T; }
+// the mr x mc tile at (r0, c0) of the matrix M of order nf to and from a tile in LDS
+__device__ inline void ceigw_tile_in(const double* M, int nf, int r0, int mr, int c0, int mc, double* T) {
+  for (int e = SMCP_TID; e < mr * mc; e += MRC_NT) T[e % mr + (e / mr) * CW_LD] = M[(r0 + e % mr) + (int64_t)(c0 + e / mr) * nf];
+}
+__device__ inline void ceigw_tile_out(double* M, int nf, int r0, int mr, int c0, int mc, const double* T) {
+  for (int e = SMCP_TID; e < mr * mc; e += MRC_NT) M[(r0 + e % mr) + (int64_t)(c0 + e / mr) * nf] = T[e % mr + (e / mr) * CW_LD];
+}
+
+// Block column j, one workgroup per clique: G_jj = R_jj R_jj^T by wg::potrf in LDS
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_potrf(CeigwArgs a, int j) {
+  extern __shared__ double mrc_lds[];
+  const CeigwDesc w = a.wd[blockIdx.x];
+  const int nf = w.nf;
+  if (j >= ceigw_nt(nf)) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  if (v.state[CW_DONE]) return;
+  double* T = mrc_lds;
+  const int o = j * CW_T, n = ceigw_tn(nf, j);
+  ceigw_tile_in(v.G, nf, o, n, o, n, T);
+  __syncthreads();
+  if (wg::potrf(n, T, CW_LD)) {                        // (uniform)
+    if (SMCP_TID == 0) v.state[CW_NOTPD] = v.state[CW_DONE] = 1;
+    return;
+  }
+  for (int e = SMCP_TID; e < n * n; e += MRC_NT) v.G[(o + e % n) + (int64_t)(o + e / n) * nf] = e % n >= e / n ? T[e % n + (e / n) * CW_LD] : 0.0;
+}
+
+// Block column j, tile i = j + 1 + blockIdx.x of clique blockIdx.y: G_ij <- G_ij R_jj^-T
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_panel(CeigwArgs a, int j) {
+  extern __shared__ double mrc_lds[];
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const int nf = w.nf, i = j + 1 + (int)blockIdx.x;
+  if (i >= ceigw_nt(nf)) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  if (v.state[CW_DONE]) return;
+  double* T = mrc_lds;
+  double* R = T + CW_T * CW_LD;
+  const int oi = i * CW_T, mi = ceigw_tn(nf, i), oj = j * CW_T;
+  ceigw_tile_in(v.G, nf, oi, mi, oj, CW_T, T);
+  ceigw_tile_in(v.G, nf, oj, CW_T, oj, CW_T, R);
+  __syncthreads();
+  wg::trsm_rlT(mi, CW_T, R, CW_LD, T, CW_LD);
+  ceigw_tile_out(v.G, nf, oi, mi, oj, CW_T, T);
+}
+
+// Block column j, clique blockIdx.y, blockIdx.x: tile (i, l) = (j + 1 + P, j + 1 + Q), P >= Q: G_il <- G_il - G_ij G_lj^T
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_trail(CeigwArgs a, int j) {
+  extern __shared__ double mrc_lds[];
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const int nf = w.nf;
+  int x = blockIdx.x, Pi = 0;
+  while (x > Pi) { x -= Pi + 1; ++Pi; }
+  const int i = j + 1 + Pi, l = j + 1 + x;
+  if (i >= ceigw_nt(nf)) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  if (v.state[CW_DONE]) return;
+  double* Li = mrc_lds;
+  double* Ll = Li + CW_T * CW_LD;
+  const int oi = i * CW_T, mi = ceigw_tn(nf, i), ol = l * CW_T, ml = ceigw_tn(nf, l), oj = j * CW_T;
+  ceigw_tile_in(v.G, nf, oi, mi, oj, CW_T, Li);
+  ceigw_tile_in(v.G, nf, ol, ml, oj, CW_T, Ll);
+  __syncthreads();
+  double* G = v.G;
+  wg_mma(mi, ml, CW_T, [=](int r, int kk) { return Li[r + kk * CW_LD]; }, [=](int kk, int c) { return Ll[c + kk * CW_LD]; },
+         [=](int r, int c, double s) { G[(oi + r) + (int64_t)(ol + c) * nf] -= s; });
+}
+
+// One workgroup per slab of CW_T columns (LEFT: F <- R^-1 F) or of CW_T rows (F <- F R^-T) of clique blockIdx.y: it walks the
+// tiles of its slab in order, tile t <- (tile t - the sum over k < t, ascending, of the products with the tiles it has
+// already solved) and then the solve with R_tt, in LDS; the slabs of a launch are independent.
+template <bool LEFT>
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_solve(CeigwArgs a) {
+  extern __shared__ double mrc_lds[];
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const int nf = w.nf, nt = ceigw_nt(nf), sl = blockIdx.x;
+  if (sl >= nt) return;
+  const CeigwView v = ceigw_view(w, a.ws);
+  if (v.state[CW_DONE]) return;
+  double* T = mrc_lds;
+  double* R = T + CW_T * CW_LD;
+  double* X = R + CW_T * CW_LD;
+  const int os = sl * CW_T, ms = ceigw_tn(nf, sl);
+  for (int t = 0; t < nt; ++t) {
+    const int ot = t * CW_T, mt = ceigw_tn(nf, t);
+    if (LEFT) ceigw_tile_in(v.F, nf, ot, mt, os, ms, T);
+    else ceigw_tile_in(v.F, nf, os, ms, ot, mt, T);
+    for (int k = 0; k < t; ++k) {
+      const int ok = k * CW_T;
+      __syncthreads();                                 // (T is loaded, the product before this one has read R and X)
+      ceigw_tile_in(v.G, nf, ot, mt, ok, CW_T, R);     // R_tk
+      if (LEFT) ceigw_tile_in(v.F, nf, ok, CW_T, os, ms, X);
+      else ceigw_tile_in(v.F, nf, os, ms, ok, CW_T, X);
+      __syncthreads();
+      if (LEFT)
+        wg_mma(mt, ms, CW_T, [=](int r, int kk) { return R[r + kk * CW_LD]; }, [=](int kk, int c) { return X[kk + c * CW_LD]; },
+               [=](int r, int c, double s) { T[r + c * CW_LD] -= s; });
+      else
+        wg_mma(ms, mt, CW_T, [=](int r, int kk) { return X[r + kk * CW_LD]; }, [=](int kk, int c) { return R[c + kk * CW_LD]; },
+               [=](int r, int c, double s) { T[r + c * CW_LD] -= s; });
+    }
+    __syncthreads();
+    ceigw_tile_in(v.G, nf, ot, mt, ot, mt, R);         // R_tt
+    __syncthreads();
+    if (LEFT) {
+      wg::trsm_llN(mt, ms, R, CW_LD, T, CW_LD);
+      ceigw_tile_out(v.F, nf, ot, mt, os, ms, T);
+    } else {
+      wg::trsm_rlT(ms, mt, R, CW_LD, T, CW_LD);
+      ceigw_tile_out(v.F, nf, os, ms, ot, mt, T);
+    }
+    __threadfence_block();                             // the tile is read back from memory as X by this workgroup
+    __syncthreads();
+  }
+}
+
+// F <- (F + F^T) / 2 on gridDim.x workgroups per clique: the thread of an entry below the diagonal writes it and its mirror
+// image (the expression of k_ceig)
+__global__ void __launch_bounds__(MRC_NT) k_ceigw_symm(CeigwArgs a) {
+  const CeigwDesc w = a.wd[blockIdx.y];
+  const CeigwView v = ceigw_view(w, a.ws);
+  if (v.state[CW_DONE]) return;
+  const int nf = w.nf;
+  for (int e = blockIdx.x * MRC_NT + SMCP_TID; e < nf * nf; e += gridDim.x * MRC_NT) {
+    const int i = e % nf, j = e / nf;
+    if (i > j) {
+      const double s = 0.5 * (v.F[i + (int64_t)j * nf] + v.F[j + (int64_t)i * nf]);
+      v.F[i + (int64_t)j * nf] = s;
+      v.F[j + (int64_t)i * nf] = s;
+    }
+  }
+}
+
 // |F|_F and the stop threshold, the largest |off-diagonal entry| of F into slot 0 (zeros into the others), the status: one
-// workgroup per clique; a non-finite |F|_F flags the clique at once
+// workgroup per clique; a non-finite |F|_F flags the clique at once.  Pencil mode: CW_NOTPD is kept as the reduction left
+// it, and a clique that carries it stays ended (and is not one that did not converge).
 __global__ void __launch_bounds__(MRC_NT) k_ceigw_begin(CeigwArgs a) {
   __shared__ double red[MRC_NT];
   const CeigwDesc w = a.wd[blockIdx.x];
@@ -133,12 +291,14 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_begin(CeigwArgs a) {
   off = ceig_reduce(off, true, red);
   for (int s = SMCP_TID; s < w.h * (w.h + 1) / 2; s += MRC_NT) v.slot[s] = s == 0 ? off : 0.0;
   if (SMCP_TID == 0) {
-    const int bad = !(fro < INFINITY);
+    const int notpd = a.pencil ? v.state[CW_NOTPD] : 0;
+    const int bad = !notpd && !(fro < INFINITY);
     v.st[0] = fro;
     v.st[1] = DBL_EPSILON * fro;
     for (int s = 0; s < CW_STATE; ++s) v.state[s] = 0;
-    v.state[CW_DONE] = bad;
+    v.state[CW_DONE] = bad | notpd;
     v.state[CW_NOCONV] = bad;
+    v.state[CW_NOTPD] = notpd;
   }
 }
 
@@ -287,7 +447,8 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_apply(CeigwArgs a, int r, int 
 // The end of a clique, one workgroup each: the rank sort of the diagonal into w (and sw, rk, col for k_ceigw_out), with
 // vmode 1 the counts of the eigenvalues outside [lo, hi] and pinfo as k_ceig_vec leaves it; the block sweeps into rank, the
 // status into flag.  A clique that did not converge: NaN in w and pinfo.  The cone pass (vmode CW_VMODE_CONE): the number of
-// eigenvalues < 0 into the status words, and pinfo, rank and flag are left to k_ceigw_cone_finish.
+// eigenvalues < 0 into the status words, and pinfo, rank and flag are left to k_ceigw_cone_finish.  Pencil mode: a clique
+// whose B_gg is not positive definite (CW_NOTPD) gets NaN in w and CEIG_NOT_PD in flag, as k_ceig leaves it.
 __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
   __shared__ double red[MRC_NT];
   const CeigwDesc w = a.wd[blockIdx.x];
@@ -295,8 +456,8 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
   const int nf = w.nf, k = w.k;
   const CliqueDesc d = a.m.cl[k];
   double* wout = a.m.w + d.rows;
-  const int noconv = v.state[CW_NOCONV];
-  if (!noconv) {
+  const int noconv = v.state[CW_NOCONV], notpd = a.pencil ? v.state[CW_NOTPD] : 0;
+  if (!noconv && !notpd) {
     double* dg = v.ev;
     for (int i = SMCP_TID; i < nf; i += MRC_NT) dg[i] = v.F[i + (int64_t)i * nf];
     __syncthreads();
@@ -338,7 +499,7 @@ __global__ void __launch_bounds__(MRC_NT) k_ceigw_sort(CeigwArgs a) {
   }
   if (SMCP_TID == 0 && a.m.vmode != CW_VMODE_CONE) {     // (the cone pass: k_ceigw_cone_finish)
     a.m.rank[k] = v.state[CW_SWEEPS];
-    a.m.flag[k] = noconv ? CEIG_NO_CONV : 0;
+    a.m.flag[k] = notpd ? CEIG_NOT_PD : noconv ? CEIG_NO_CONV : 0;
   }
 }
 

@@ -8,9 +8,14 @@ interleaved in one process: every repetition runs every setting once.  Warm, syn
 (min - max) of --reps (5).  Also recorded per setting: the cliques on the wide route, the most sweeps, and the largest
 difference of w from the setting 0 in nf eps max|w|.
 
-    python tools/clique_wide_time.py [--reps N] [--out FILE] [--settings 0,65,...] [--once SETTING] [case ...]
+    python tools/clique_wide_time.py [--reps N] [--out FILE] [--settings 0,65,...] [--once SETTING] [--pencil] [case ...]
 
---once SETTING: one warm-up and one clique_project under that setting and nothing else (for a kernel trace of the route).
+--once SETTING: one warm-up and one clique_project under that setting and nothing else (for a kernel trace of the route);
+with --pencil the two calls are clique_eigvalsh(A, B).
+--pencil: the pencil form instead -- clique_eigvalsh(A, B) and max_step(B, D) with B = L L^T of
+tools/clique_project_time.py (every clique block positive definite), A = X and D the noise of X -- at the settings 0 and 65
+(and 90 on synth50k), interleaved in the same way; the difference of w from the setting 0 is counted in nf eps max|w|
+cond(B_gg) units of the setting 0's own w.  Writes profiles/pencil_wide_bench.json unless --out names another file.
 """
 import json
 import os
@@ -38,6 +43,59 @@ def make(name):
     chordal.llt(S)
     noise = np.random.default_rng(2).standard_normal(symb.blklen) * (np.bincount(symb.ccs_to_blk(), minlength=symb.blklen) > 0)
     return symb, cspmatrix(symb, S.blkval + 0.3 * torch.from_numpy(noise).cuda())
+
+
+def make_pencil(name):
+    """(symb, A, B, D): B = L L^T, positive definite on every clique; A = B + 0.3 noise, D = the noise"""
+    symb = CASES[name]()
+    symb.device_init(0, 1)
+    B = cspmatrix(symb, torch.from_numpy(problems.random_factor_blkval(symb, 1)).cuda())
+    chordal.llt(B)
+    noise = np.random.default_rng(2).standard_normal(symb.blklen) * (np.bincount(symb.ccs_to_blk(), minlength=symb.blklen) > 0)
+    D = cspmatrix(symb, torch.from_numpy(noise).cuda())
+    return symb, cspmatrix(symb, B.blkval + 0.3 * D.blkval), B, D
+
+
+PENCIL_SETTINGS = {"config4": [0, 65], "synth50k": [0, 65, 90]}
+
+
+def run_pencil(name, reps, settings):
+    symb, A, B, D = make_pencil(name)
+    calls = {"clique_eigvalsh_pencil": lambda: chordal.clique_eigvalsh(A, B), "max_step": lambda: chordal.max_step(B, D, return_clique=True)}
+    nf = np.diff(symb.rowptr)
+    res = {"case": name, "n": symb.n, "nsn": symb.Nsn, "widest_clique": int(nf.max()), "reps": reps, "form": "pencil", "settings": {}}
+    times = {s: {c: [] for c in calls} for s in settings}
+    w0 = None
+    for s in settings:                                                    # first calls: buffers, and what does not change
+        chordal.tune(symb, chordal.TUNE_CEIG_WIDE, s)
+        first = {c: wall(f)[0] for c, f in calls.items()}
+        w = chordal.clique_eigvalsh(A, B)
+        entry = {"wide_cliques": chordal.clique_eig_wide(symb), "launch_groups": chordal.clique_eig_groups(symb),
+                 "most_sweeps": chordal.clique_eig_sweeps(symb), "first_call_ms": first, "max_step": list(chordal.max_step(B, D, return_clique=True))}
+        if s == 0:
+            w0 = w
+        elif w0 is not None:
+            d = (w - w0).abs().cpu().numpy()
+            a = w0.abs().cpu().numpy()
+            entry["w_against_setting_0_units"] = float(max(
+                d[symb.rowptr[k]:symb.rowptr[k + 1]].max() / (nf[k] * np.finfo(float).eps * max(a[symb.rowptr[k]:symb.rowptr[k + 1]].max(), 1e-300))
+                for k in range(symb.Nsn)))
+        entry["kernels_of_one_clique_eigvalsh_pencil"] = kernel_ms(symb, calls["clique_eigvalsh_pencil"])
+        res["settings"][str(s)] = entry
+        print("%s pencil setting %d: %s" % (name, s, json.dumps(entry)), flush=True)
+    for rep in range(reps):
+        for s in settings:
+            chordal.tune(symb, chordal.TUNE_CEIG_WIDE, s)
+            for c, f in calls.items():
+                times[s][c].append(wall(f)[0])
+        print("%s pencil repetition %d done" % (name, rep), flush=True)
+    chordal.tune(symb, chordal.TUNE_CEIG_WIDE, 0)
+    for s in settings:
+        for c in calls:
+            res["settings"][str(s)][c] = stats(times[s][c])
+        print("%s pencil setting %d: " % (name, s) + ", ".join("%s %.2f ms (%.2f - %.2f)" % (
+            c, res["settings"][str(s)][c]["median_ms"], min(times[s][c]), max(times[s][c])) for c in calls), flush=True)
+    return res
 
 
 def run(name, reps, settings):
@@ -100,9 +158,23 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     reps = int(take(args, "--reps", 5))
     out = take(args, "--out", None)
-    settings = [int(v) for v in take(args, "--settings", ",".join(map(str, SETTINGS))).split(",")]
+    pencil = "--pencil" in args
+    if pencil:
+        args.remove("--pencil")
+        out = out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pencil_wide_bench.json")
+    chosen = take(args, "--settings", None)
+    settings = [int(v) for v in (chosen or ",".join(map(str, SETTINGS))).split(",")]
     once = take(args, "--once", None)
     torch.cuda.set_device(0)
+    if once is not None and pencil:
+        for name in (args or ["config4"]):
+            symb, A, B, D = make_pencil(name)
+            chordal.tune(symb, chordal.TUNE_CEIG_WIDE, int(once))
+            t1 = wall(lambda: chordal.clique_eigvalsh(A, B))[0]
+            t2 = wall(lambda: chordal.clique_eigvalsh(A, B))[0]
+            print("%s setting %s: clique_eigvalsh(A, B) %.2f ms, then %.2f ms; %d wide cliques, %d sweeps at most"
+                  % (name, once, t1, t2, chordal.clique_eig_wide(symb), chordal.clique_eig_sweeps(symb)), flush=True)
+        sys.exit(0)
     if once is not None:
         for name in (args or ["config4"]):
             symb, X = make(name)
@@ -114,7 +186,10 @@ if __name__ == "__main__":
         sys.exit(0)
     results = []
     for name in (args or ["config4", "synth50k"]):
-        results.append(run(name, reps, settings))
+        if pencil:
+            results.append(run_pencil(name, reps, settings if chosen else PENCIL_SETTINGS.get(name, [0, 65])))
+        else:
+            results.append(run(name, reps, settings))
         if out:
             with open(out, "w") as f:
                 json.dump(results, f, indent=1)
