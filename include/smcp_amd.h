@@ -36,6 +36,8 @@ typedef struct csp_ctx csp_ctx;
                              of another workgroup: the launch gave up instead of hanging (never seen; the results are invalid) */
 #define SMCP_ENOCONV (-7) /* the Jacobi iteration of csp_clique_eigvalsh / csp_clique_eigh / csp_clique_project did not converge
                              on some clique within 30 sweeps, or the clique block holds a non-finite entry */
+#define SMCP_ESUPPORT (-8) /* csp_chol_update: a column of V has a nonzero outside the clique its first nonzero selects */
+#define SMCP_EVALUE (-9)   /* csp_chol_update: a column of V, or its coefficient, holds a NaN or an infinity */
 
 /* ---- symbolic layer (host only, no GPU needed) ------------------------------------- */
 
@@ -216,6 +218,34 @@ int csp_lowrank_apply(csp_ctx* ctx, const double* L, const double* W, int64_t ld
                       int64_t ldb, int64_t nrhs, int op, void* stream);
 /* *out (host) = log det M = 2 csp_logdiagsum(L) + sum of log t_j.  Synchronises the stream. */
 int csp_lowrank_logdet(csp_ctx* ctx, const double* L, const double* state, double* out, void* stream);
+/* Rank-k update and downdate of the factor itself: L (as csp_cholesky leaves it) is overwritten so that L L^T becomes
+ * L L^T + V diag(a) V^T.  V: dense n x k in the layout of csp_trsm (column j at V + j ldv, ldv >= n, rows in the permuted
+ * order), 1 <= k <= 64, only read, entries between n and ldv of a column neither read nor touched; a_host: k coefficients on
+ * the HOST, NULL for all ones; a_j < 0 is a downdate, a_j = 0 leaves its column out.  Every column v must have its support
+ * inside one clique: with j0 its first nonzero and s the supernode of column j0, all its nonzeros lie in the rows [N_s; A_s]
+ * (csp_clique_support finds s on the host) -- the condition under which the storage of L holds the new factor without fill.
+ * The columns with a_j > 0 are taken first, then those with a_j < 0, each group in the caller's order (the order of
+ * csp_lowrank_factor); the arithmetic is that of successive rank-one updates of the whole factor, whatever k.
+ * Two launches whatever the tree and whatever k; cliques outside the leaf-to-root paths of the columns are not written, nor
+ * is a panel column whose rotations are all the identity.  No floating-point atomics: the same arguments give the same bits.
+ * Synchronises the stream and returns
+ *   0              L holds the new factor;
+ *   1 + j          the downdate by column j (caller's numbering) met (l - w)(l + w) <= 0: the matrix is no longer positive
+ *                  definite and L IS NOT USABLE (as after a failed csp_cholesky: keep a copy where that matters);
+ *   SMCP_ESUPPORT  a column violates the support condition, SMCP_EVALUE a column or its coefficient is not finite: L is bit for
+ *                  bit what it was (the columns are checked on the device before anything is written); the first such column
+ *                  is what csp_chol_update_info reports;
+ *   SMCP_EINVAL    a null L or V, k outside 1 .. 64, ldv < n, a replicated context or one under a subtree partition over
+ *                  more than one rank; SMCP_ENODEV without a device.
+ * Whatever the library had derived from the old contents at L's address is dropped, as by csp_touch. */
+int csp_chol_update(csp_ctx* ctx, double* L, const double* V, int64_t ldv, int64_t k, const double* a_host, void* stream);
+/* *column = the column of V (caller's numbering) that the last csp_chol_update on this context refused or failed at, -1 when
+ * it returned 0 or an argument error.  Host only. */
+int csp_chol_update_info(const csp_ctx* ctx, int64_t* column);
+/* The clique whose rows contain all of idx[0 .. cnt) (permuted order) and whose supernode holds the smallest of them: the s
+ * of csp_chol_update for a column with that support; -1 when there is none (also for cnt = 0, an index outside 0 .. n - 1, a
+ * null idx or a replicated context).  Host only: needs no device. */
+int64_t csp_clique_support(const csp_ctx* ctx, int64_t cnt, const int64_t* idx);
 /* chompack.mrcompletion(X), pass 1: *r = max over the cliques g of the numerical rank of X_gg -- the pivots of a
  * diagonally pivoted Cholesky (LAPACK pstrf semantics) above tol * max diag(X_gg).  Returns 1 + k when clique k has a
  * remaining pivot below -tol * max diag(X_gg): X has no positive semidefinite completion.  Synchronises the stream. */

@@ -15,6 +15,8 @@ from .chordal import cholesky, projected_inverse, hessian, llt, trsm, trmm, syr2
 from .chordal import clique_eigvalsh, clique_extremes  # noqa: F401
 from .chordal import clique_ptr, clique_block, clique_gather, clique_scatter, clique_multiplicity, clique_eigh, clique_project  # noqa: F401
 from .base import cone_project  # noqa: F401  (scipy matrices; the cspmatrix form is smcp_amd.chordal.cone_project)
+from .base import chol_update  # noqa: F401  (V in the original order; the device form is smcp_amd.chordal.chol_update)
+from .chordal import clique_support  # noqa: F401
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion
 
 __version__ = "0.1.0"

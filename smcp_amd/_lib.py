@@ -43,6 +43,9 @@ SIGNATURES = {
     "csp_lowrank_factor": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
     "csp_lowrank_apply": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, ctypes.c_int, c_vp]),
     "csp_lowrank_logdet": (ctypes.c_int, [c_vp, c_vp, c_vp, c_dblp, c_vp]),
+    "csp_chol_update": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]),
+    "csp_chol_update_info": (ctypes.c_int, [c_vp, c_i64p]),
+    "csp_clique_support": (c_i64, [c_vp, c_i64, c_vp]),
     "csp_mrcompletion_rank": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64p, c_vp]),
     "csp_mrcompletion": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, c_i64, c_vp, c_i64, c_vp]),
     "csp_maxcut_cuts": (ctypes.c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -615,6 +615,25 @@ def dual_margin(S, tol=1e-10, maxit=64):
     return chordal.dual_margin(Sc, tol=tol, maxit=maxit)
 
 
+def chol_update(L, V, a=None):
+    """L L^T <- L L^T + V diag(a) V^T in place for the ``cspmatrix`` factor L (as ``cholesky`` leaves it, on the device) and
+    an n x k matrix V in the ORIGINAL order (scipy sparse or anything numpy.asarray takes; a vector of length n is one
+    column), 1 <= k <= 64: V is permuted with the ordering of L.symb, uploaded, and handed to
+    smcp_amd.chordal.chol_update, whose docstring states the support condition on the columns (each inside one clique),
+    the order in which they are taken and the errors: ValueError for a column outside every clique or not finite (L
+    unchanged), ArithmeticError when a downdate leaves the cone (L not usable)."""
+    import torch
+    from . import chordal
+    Vd = np.asarray(V.toarray() if sp.issparse(V) else V, dtype=np.float64)
+    if Vd.ndim == 1:
+        Vd = Vd[:, None]
+    n = L.symb.n
+    if Vd.ndim != 2 or Vd.shape[0] != n:
+        raise ValueError("chol_update: V must be n x k with n = %d" % n)
+    Vp = np.ascontiguousarray(Vd[np.asarray(L.symb.p)].T)
+    chordal.chol_update(L, torch.from_numpy(Vp).to(L.blkval.device), a)
+
+
 def maxcut_round(P, X, trials=64, seed=0, tol=1e-8):
     """Goemans-Williamson rounding of a max-cut relaxation (maxcut_SDP: C = -(Diag(W 1) - W) / 4) at its solution X
     (scipy sparse, e.g. sol['x']): Y = mrcompletion(X, tol), `trials` Gaussian directions g_t drawn with numpy's

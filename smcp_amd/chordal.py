@@ -903,6 +903,80 @@ def lowrank_factor(L, V, a=None):
     return LowRankFactor(L, W, state)
 
 
+CHOL_UPDATE_KMAX = 64
+_E_SUPPORT, _E_VALUE = -8, -9        # include/smcp_amd.h: SMCP_ESUPPORT, SMCP_EVALUE
+
+
+def clique_support(symb, idx):
+    """The clique k whose rows [N_k; A_k] contain every index of `idx` (PERMUTED order) and whose supernode N_k holds the
+    smallest of them, or -1 when there is none: the clique that a column of V with that support selects in ``chol_update``,
+    which accepts the column exactly when this is not -1.  Needs no device (csp_clique_support)."""
+    import numpy as np
+    ix = np.ascontiguousarray(np.asarray(idx, dtype=np.int64).ravel())
+    return int(_lib.lib().csp_clique_support(symb.handle, ix.shape[0], ix.ctypes.data_as(ctypes.c_void_p)))
+
+
+def chol_update(L, V, a=None):
+    """Rank-k update and downdate of the factor itself: L (a ``cspmatrix`` as ``cholesky`` leaves it) is overwritten in place
+    so that L L^T becomes L L^T + V diag(a) V^T.  V: a float64 device tensor of shape (k, >= n), 1 <= k <= 64, with
+    stride(1) == 1, laid out as for ``trsm`` / ``trmm`` / ``lowrank_factor`` (row j is column j of V, rows in the PERMUTED
+    order); it is not written and its entries beyond n are neither read nor touched.  a: k floats (None: all ones); a
+    negative entry is a downdate, a zero entry leaves its column out.
+
+    Every column of V must have its support inside one clique: with j0 its first nonzero and s the supernode of column
+    j0, all its nonzeros lie in the rows of clique s (``clique_support`` finds s, or -1).  That is the condition under which
+    the new factor has no fill; ``lowrank_factor`` takes any V and leaves L alone.  A column that violates it, or a NaN or
+    an infinity in V or a, is a ValueError naming the column, and L is then bit for bit what it was: the columns are checked
+    on the device before anything is written.
+
+    The columns with a_j > 0 are taken first, then those with a_j < 0, each group in the caller's order; the arithmetic is
+    that of k successive rank-one updates, cliques outside the leaf-to-root paths of the columns are not written, and the
+    same arguments give the same bits.  Two launches whatever the tree and k.  What the library had derived from the old
+    contents of L (the inverse-form factor a ``hessian`` left behind) is dropped.
+
+    ArithmeticError naming the column when a downdate leaves the cone (l_cc^2 - w_c^2 <= 0).  L IS THEN NOT USABLE, as
+    after a failed ``cholesky``: keep ``L.copy()`` where that matters."""
+    symb = L.symb
+    if not isinstance(V, torch.Tensor) or V.dim() != 2:
+        raise ValueError("chol_update: V must be a 2-D torch tensor of shape (k, n)")
+    k = int(V.shape[0])
+    if k < 1 or k > CHOL_UPDATE_KMAX:
+        raise ValueError("chol_update: k = %d is outside 1 .. %d" % (k, CHOL_UPDATE_KMAX))
+    if V.dtype != torch.float64:
+        raise ValueError("chol_update: float64 is needed, got %s" % V.dtype)
+    if V.shape[1] < symb.n:
+        raise ValueError("chol_update: V has %d rows, the pattern has %d" % (V.shape[1], symb.n))
+    if V.stride(1) != 1 or (k > 1 and V.stride(0) < symb.n):
+        raise ValueError("chol_update: stride(1) == 1 and stride(0) >= n are needed")
+    if not V.is_cuda or not L.blkval.is_cuda or L.blkval.device != V.device:
+        raise ValueError("chol_update: L and V must be on the same device")
+    ah = None
+    if a is not None:
+        coef = [float(x) for x in a]
+        if len(coef) != k:
+            raise ValueError("chol_update: a must hold %d numbers" % k)
+        for j, x in enumerate(coef):
+            if x != x or abs(x) == float("inf"):
+                raise ValueError("chol_update: the coefficient of column %d is not finite" % j)
+        ah = (ctypes.c_double * k)(*coef)
+    _ensure(symb)
+    lib = _lib.lib()
+    L.touched()
+    try:
+        rc = lib.csp_chol_update(symb.handle, L.blkval.data_ptr(), V.data_ptr(), V.stride(0) if k > 1 else max(V.stride(0), symb.n),
+                                 k, ah, _stream())
+    finally:
+        note_cache(symb, L)
+    if rc > 0:
+        raise ArithmeticError("chol_update: the downdate by column %d leaves the cone; L is not usable" % (rc - 1))
+    if rc in (_E_SUPPORT, _E_VALUE):
+        col = ctypes.c_int64(-1)
+        lib.csp_chol_update_info(symb.handle, ctypes.byref(col))
+        raise ValueError("chol_update: column %d of V %s; L is unchanged" % (
+            col.value, "has a nonzero outside the clique of its first nonzero" if rc == _E_SUPPORT else "is not finite"))
+    _chk(rc, "chol_update")
+
+
 def dot(X, Y):
     _ensure(X.symb)
     out = ctypes.c_double(0.0)

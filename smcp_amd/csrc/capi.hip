@@ -45,6 +45,7 @@
 #include "front_syr2k.hip"
 #include "front_symm.hip"
 #include "front_lowrank.hip"
+#include "front_update.hip"
 #include "front_lanczos.hip"
 
 using namespace smcp;
@@ -3001,6 +3002,7 @@ const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COU
 }  // extern "C"
 
 #include "lowrank.hip"
+#include "chol_update.hip"
 #include "lanczos.hip"
 #include "kkt.hip"
 #include "kkt_many.hip"

@@ -244,6 +244,7 @@ struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
   double fam_meanterms = 0;   // ... and their mean over all (family, constraint) pairs (what the entry-driven sweeps cost in proportion to)
   double* trsm_x = nullptr; int64_t trsm_x_len = 0;   // scratch image of the right-hand sides of csp_trsm (tile-product route) and of csp_trmm
   double* lr_ws = nullptr; int64_t lr_ws_len = 0;     // partial Gram products of the low-rank factor (lowrank.hip: slabs x k x columns)
+  double* cu_ws = nullptr; int64_t cu_ws_len = 0;     // csp_chol_update (chol_update.hip): flags, visit bytes, then the k x n image of V that becomes w
   DenseChol chol;
   double* sw = nullptr;      // blklen : sqrt of the inner-product weights (Gram path)
   int lg_rec = 0;                                                     // doubles per child of the per-step tables (lg_tab)
@@ -384,6 +385,7 @@ struct csp_ctx : smcp::PartitionTables {
   std::vector<ConeGroup> cone_groups;
   struct PsdLevel { int64_t b1 = 0, b2 = 0, e2 = 0; };   // csp_psdcompletion: tasks [b1, b2) of step 1 and [b2, e2) of step 2
   std::vector<PsdLevel> psd_lev;        // per level with fill work, root first
+  int64_t cu_column = -1;               // csp_chol_update_info: the column of V the last csp_chol_update refused or failed at (-1: none)
   int64_t ntrial = 1;                   // copies of the pattern in S (csp_symbolic_replicate): one failure flag per copy
   // side streams for clique-local launches that do not depend on each other (Fork in capi.hip): created on first use
   hipStream_t aux_stream[2] = {nullptr, nullptr};
