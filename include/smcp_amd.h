@@ -317,6 +317,19 @@ int csp_clique_gather(csp_ctx* ctx, const double* x, double* Z, void* stream);
  * of its child list, no atomics: the same input gives the same bits.  SMCP_EINVAL for a null x or Z, a replicated or
  * partitioned context, or x overlapping Z.  Does not synchronise. */
 int csp_clique_scatter(csp_ctx* ctx, const double* Z, double* x, void* stream);
+/* Z_k = P_k P_k^T for every clique: the Agler decomposition of L L^T (no reference counterpart; CHOMPACK has none).
+ * L (device, blkval) is a factor as csp_cholesky leaves it and is only read; Z (device, packed clique blocks) is written.
+ * Clique k has nn own columns and nf = nn + na rows, its panel P is nf x nn, column-major with leading dimension nf, at
+ * blkptr[k] of L.  With Pt[m, c] = P[m, c] for m >= c and 0 otherwise (the slots m < c < nn of L are never read)
+ *     Z_k[i, j] = sum_{c = 0}^{min(i, j, nn - 1)} Pt[i, c] Pt[j, c],    0 <= i, j < nf,    c ascending,
+ * stored at Z + qptr[k] + i + j nf: the full symmetric block, both triangles carrying the same bits, every entry of Z with
+ * exactly one writer.  Every Z_k is positive semidefinite of rank <= nn and sum_k E_k Z_k E_k^T = L L^T: csp_clique_scatter
+ * of Z is csp_llt of L to rounding.  One launch, two when the large fronts take the tile products (everything runs on the
+ * plain FMA kernel under CSP_TUNE_DETERMINISTIC), whatever the tree; no atomics: the same L gives the same bits.  Nothing
+ * cached for L is dropped or created.  A positive semidefinite matrix that is singular has no factor here and is out of
+ * reach of this call.  SMCP_EINVAL for a null L or Z, a replicated or partitioned context, or Z overlapping L.  Does not
+ * synchronise. */
+int csp_clique_decompose(csp_ctx* ctx, const double* L, double* Z, void* stream);
 /* Eigenvectors of the clique blocks: w and ext as csp_clique_eigvalsh gives them in standard form (the same bits); Q
  * (device, packed clique blocks): column j of block k is a unit eigenvector of A_gg for w[rowptr[k] + j].  The Jacobi
  * iteration of csp_clique_eigvalsh with the rotations accumulated, in the slot of its pencil form; signs and the basis

@@ -17,6 +17,7 @@ from .chordal import clique_ptr, clique_block, clique_gather, clique_scatter, cl
 from .base import cone_project  # noqa: F401  (scipy matrices; the cspmatrix form is smcp_amd.chordal.cone_project)
 from .base import chol_update  # noqa: F401  (V in the original order; the device form is smcp_amd.chordal.chol_update)
 from .chordal import clique_support  # noqa: F401
+from .base import clique_decompose  # noqa: F401  (scipy matrices; the cspmatrix form is smcp_amd.chordal.clique_decompose)
 # the CHOMPACK-level in-place completion (factor of the inverse) is smcp_amd.chordal.completion
 
 __version__ = "0.1.0"

@@ -56,6 +56,7 @@ SIGNATURES = {
     "csp_clique_ptr": (ctypes.c_int, [c_vp, c_vp]),
     "csp_clique_gather": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "csp_clique_scatter": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
+    "csp_clique_decompose": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "csp_clique_eigh": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "csp_clique_project": (ctypes.c_int, [c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp]),
     "csp_cone_project_steps": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_double, ctypes.c_double, c_i64, c_i64, c_vp, c_vp]),

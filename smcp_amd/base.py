@@ -615,6 +615,29 @@ def dual_margin(S, tol=1e-10, maxit=64):
     return chordal.dual_margin(Sc, tol=tol, maxit=maxit)
 
 
+def clique_decompose(S):
+    """(cliques, blocks) with S = sum_k E_k blocks[k] E_k^T for the sparse symmetric positive definite S (scipy sparse, either
+    triangle or both) on a chordal pattern, every blocks[k] positive semidefinite (Agler's theorem): ``cholesky`` of S,
+    then smcp_amd.chordal.clique_decompose, whose docstring states the blocks.  cliques[k] holds the row indices of clique k
+    in the ORIGINAL numbering, in the order of the rows and columns of blocks[k], a numpy nf x nf array of rank at most the
+    number of columns the clique owns.  ValueError for a pattern that is not chordal, ArithmeticError (that of ``cholesky``)
+    when S is not positive definite: a singular positive semidefinite S is out of reach of this call."""
+    from . import chordal
+    Sc = _on_chordal_pattern([S], "clique_decompose")[0]
+    chordal.cholesky(Sc)
+    symb = Sc.symb
+    Z = chordal.clique_decompose(Sc).cpu().numpy()
+    q = chordal.clique_ptr(symb)
+    p = np.asarray(symb.p)
+    rowptr, rowidx = np.asarray(symb.rowptr), np.asarray(symb.rowidx)
+    cliques, blocks = [], []
+    for k in range(symb.Nsn):
+        rows = rowidx[rowptr[k]:rowptr[k + 1]]
+        cliques.append(p[rows])
+        blocks.append(Z[q[k]:q[k + 1]].reshape((len(rows), len(rows)), order="F").copy())
+    return cliques, blocks
+
+
 def chol_update(L, V, a=None):
     """L L^T <- L L^T + V diag(a) V^T in place for the ``cspmatrix`` factor L (as ``cholesky`` leaves it, on the device) and
     an n x k matrix V in the ORIGINAL order (scipy sparse or anything numpy.asarray takes; a vector of length n is one

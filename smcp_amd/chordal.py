@@ -357,6 +357,37 @@ def clique_scatter(symb, Z, reduce="sum"):
     return X
 
 
+def clique_decompose(L, out=None):
+    """The factor as a sum of positive semidefinite clique blocks (Agler's theorem read off the supernodal factor): a packed
+    block tensor Z (``clique_ptr``; the layout and dtype of ``clique_gather``).  L is a cspmatrix read as a factor, as
+    ``cholesky`` leaves it.  Clique k has nn own columns and nf = nn + na rows and its panel P is nf x nn; with
+    Pt[m, c] = P[m, c] for m >= c and 0 otherwise (the slots of blkval above the diagonal of a supernode's diagonal block
+    are never read)
+        Z_k[i, j] = sum over c = 0 .. min(i, j, nn - 1), ascending, of Pt[i, c] Pt[j, c],        0 <= i, j < nf,
+    the full symmetric block, both triangles with the same bits.  Three properties: the blocks sum to the matrix,
+    sum_k E_k Z_k E_k^T = L L^T, so ``clique_scatter(symb, Z, "sum")`` is ``llt(L)`` to rounding; every Z_k is positive
+    semidefinite; and its rank is at most nn.  With ``clique_gather`` this is the duality of the two cones:
+    <X, L L^T> = sum_k <X_gg, Z_k>.  On the factor that ``completion(X)`` leaves the call decomposes the inverse of the
+    completion.  L is only read, and nothing cached for it is dropped or created.  One launch, two when the large fronts take
+    the tile products (under ``tune(symb, TUNE_DETERMINISTIC, 1)`` everything runs on the plain FMA kernel), whatever the
+    tree; no atomics, every entry has one writer: the same L gives the same bits from call to call.  out: a packed block
+    tensor on the device that is written and returned (ValueError for anything else, or for one that shares memory with L).
+    A positive semidefinite matrix that is singular has no factor here, and so is out of reach of this call: the
+    decomposition of such a matrix (an optimal dual slack, say) needs a semidefinite sweep of its own
+    (csp_clique_decompose)."""
+    symb = L.symb
+    _ensure(symb)
+    if out is None:
+        out = torch.empty(int(clique_ptr(symb)[-1]), dtype=torch.float64, device=L.blkval.device)
+    elif not _packed(symb, out, "clique_decompose").is_cuda:
+        raise ValueError("clique_decompose: out is not a device tensor")
+    rc = _lib.lib().csp_clique_decompose(symb.handle, L.blkval.data_ptr(), out.data_ptr(), _stream())
+    if rc == -1:
+        raise ValueError("clique_decompose: out overlaps L, or the Symbolic is replicated or partitioned")
+    _chk(rc, "clique_decompose")
+    return out
+
+
 def clique_multiplicity(symb):
     """Per slot of blkval the number of cliques that hold the entry, a float64 device tensor: the scatter of all-ones
     blocks, made once per Symbolic; 1 on the unused slots above the diagonal of a supernode's diagonal block."""

@@ -43,6 +43,7 @@
 #include "front_ceigw.hip"
 #include "front_trmm.hip"
 #include "front_syr2k.hip"
+#include "front_cdec.hip"
 #include "front_symm.hip"
 #include "front_lowrank.hip"
 #include "front_update.hip"

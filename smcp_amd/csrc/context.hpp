@@ -57,6 +57,15 @@ struct Syr2kPlan {
   int32_t* tiles = nullptr; int64_t ntiles[2] = {0, 0};
 };
 
+// the factor as a sum of clique blocks (front_cdec.hip): (clique, row chunk, column chunk, 0) items of the FMA kernel over the
+// full nf x nf blocks, those of the large fronts LAST ([0]: items without them, [1]: all), and the (clique, row tile, column
+// tile, 0) tiles with row tile >= column tile of the large fronts, which alone take the tile products, the widest front first
+struct CdecPlan {
+  bool ready = false;
+  int32_t* items = nullptr; int64_t nitems[2] = {0, 0};
+  int32_t* tiles = nullptr; int64_t ntiles = 0;
+};
+
 // products of the matrix itself (front_symm.hip): the contribution index (the contributions are all ntot partials; pos: per
 // item the positions of its row partials, then of its column partials; heavy: more than SYMM_HEAVY), and the (clique, row
 // chunk, column part, base in pos) items, those of the large fronts FIRST ([0]: theirs, [1]: all).  ntot: -1 until counted
@@ -273,6 +282,7 @@ struct DeviceCtx : ConstraintBufs, RhsWorkspaces {
   PsdPlan psd;
   TrmmPlan trmm;
   Syr2kPlan syr2k;
+  CdecPlan cdec;
   SymmPlan symm;
 };
 

@@ -1,7 +1,7 @@
 // Host drivers of the products with dense blocks: trmm (front_trmm.hip), syr2k / syrk (front_syr2k.hip) and symm
-// (front_symm.hip).  Included by capi.hip.  Each operation builds its plan (context.hpp) once per context and then runs in a
-// fixed number of launches: the products of all cliques at once and, for trmm and symm, one combining pass over a transposed
-// row index.
+// (front_symm.hip), and of the factor as a sum of clique blocks (front_cdec.hip).  Included by capi.hip.  Each operation
+// builds its plan (context.hpp) once per context and then runs in a fixed number of launches: the products of all cliques
+// at once and, for trmm and symm, one combining pass over a transposed row index.
 
 namespace {
 
@@ -159,6 +159,37 @@ int syr2k_setup(csp_ctx* c) {
   return 0;
 }
 
+// ---- the factor as a sum of clique blocks (front_cdec.hip) -----------------------------------------------------------
+// Once per context: the item list of the FMA kernel over the full nf x nf blocks and the lower tile pairs of the tile
+// products.
+int cdec_setup(csp_ctx* c) {
+  DeviceCtx& D = c->D;
+  CdecPlan& P = D.cdec;
+  if (P.ready) return 0;
+  const Symbolic& S = c->S;
+  std::vector<int32_t> items, tiles;
+  for (int pass = 0; pass < 2; ++pass) {          // items: small, large
+    for (int64_t k = 0; k < S.nsn; ++k) {
+      if ((c->large_mask[(size_t)k] != 0) != (pass == 1)) continue;
+      for (int64_t r = 0; r < (S.nf(k) + 63) / 64; ++r)
+        for (int64_t j = 0; j < (S.nf(k) + CDEC_JC - 1) / CDEC_JC; ++j) { items.push_back((int32_t)k); items.push_back((int32_t)r); items.push_back((int32_t)j); items.push_back(0); }
+    }
+    P.nitems[pass] = (int64_t)items.size() / 4;
+  }
+  const std::vector<int64_t> order = large_fronts_first(c);      // tiles: the large fronts, the only ones that take them
+  for (int64_t x = 0; x < D.nII_total; ++x)
+    for (int64_t r = 0; r < tiles64((int)S.nf(order[(size_t)x])); ++r)
+      for (int64_t j = 0; j <= r; ++j) { tiles.push_back((int32_t)order[(size_t)x]); tiles.push_back((int32_t)r); tiles.push_back((int32_t)j); tiles.push_back(0); }
+  P.ntiles = (int64_t)tiles.size() / 4;
+  if (P.nitems[1] >= ((int64_t)1 << 31) || P.ntiles >= ((int64_t)1 << 31)) return SMCP_EINVAL;     // grid dimension
+  if (int rc = dev_upload(&P.items, items, D.mem)) return rc;
+  if (int rc = dev_upload(&P.tiles, tiles, D.mem)) return rc;
+  P.ready = true;
+  return 0;
+}
+
+int qptr_setup(csp_ctx* c);      // (completions.hip, which follows this file in capi.hip)
+
 // ---- products of the matrix itself with a dense block (front_symm.hip) -----------------------------------------------
 // rows of chunk r of clique k that part p of its columns multiplies, and the columns of that part with a column partial
 // (false: the chunk lies above the diagonal of the part, no item)
@@ -298,6 +329,29 @@ int csp_syr2k(csp_ctx* c, double* X, const double* U, const double* V, int64_t k
     if (V) launch(c, KID_syr2k_mm, k_syr2k_mm<true>, dim3((unsigned)ntiles), dim3(256), st, a);
     else launch(c, KID_syr2k_mm, k_syr2k_mm<false>, dim3((unsigned)ntiles), dim3(256), st, a);
   }
+  HIPCHK(end_call(c));
+  return 0;
+}
+
+// Z_k = P_k P_k^T for every clique (front_cdec.hip): one launch per route, two when the large fronts take the tile products.
+// L is only read and nothing cached for it is touched.
+int csp_clique_decompose(csp_ctx* c, const double* L, double* Z, void* stream) {
+  if (int rc = ready(c)) return rc;
+  // (a partitioned context holds valid factors on its own cliques only)
+  if (!L || !Z || c->ntrial != 1 || c->xr_world > 1) return SMCP_EINVAL;
+  if (int rc = qptr_setup(c)) return rc;
+  if (ranges_overlap(Z, c->qlen, L, c->S.blklen())) return SMCP_EINVAL;
+  if (int rc = cdec_setup(c)) return rc;
+  DeviceCtx& D = c->D;
+  const CdecPlan& P = D.cdec;
+  hipStream_t st = (hipStream_t)stream;
+  // tile products for the large fronts; everything on the FMA kernel on the generic / deterministic route
+  const bool tiled = !use_generic(c) && use_large() && P.ntiles > 0;
+  CdecArgs a;
+  a.cl = D.cl; a.qptr = D.mrc.qptr; a.items = P.items; a.tiles = P.tiles; a.L = L; a.Z = Z;
+  a.nitems = (int)P.nitems[tiled ? 0 : 1];
+  if (a.nitems) launch(c, KID_syr2k_fma, k_cdec_fma, dim3((unsigned)((a.nitems + CDEC_WAVES - 1) / CDEC_WAVES)), dim3(64 * CDEC_WAVES), st, a);
+  if (tiled) launch(c, KID_syr2k_mm, k_cdec_mm, dim3((unsigned)P.ntiles), dim3(256), st, a);
   HIPCHK(end_call(c));
   return 0;
 }
