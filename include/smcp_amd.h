@@ -715,6 +715,19 @@ int64_t csp_profile_kinds(void);
 int64_t csp_profile_read(csp_ctx* ctx, double* ms, int64_t* count);
 const char* csp_profile_kernel_name(int kid);
 
+/* ---- launch census: launches per kernel FUNCTION ------------------------------------------------ */
+/* The ids of csp_profile_* stand for groups of kernels (a template's instantiations, the kernels of a unit launched
+ * under one id).  The census counts every launch under the kernel function that was launched, one entry per template
+ * instantiation.  Off by default; when on, a launch costs one counter increment (no events, no name look-up).
+ * csp_census_enable needs no device, so it may be called before csp_device_init to see the set-up kernels. */
+int csp_census_enable(csp_ctx* ctx, int on);
+/* Synchronises as csp_profile_read does, then writes one line "mangled<TAB>pretty<TAB>count\n" per kernel launched
+ * since the last successful read (a NUL-terminated text, sorted by mangled name) and clears the counts.  pretty is the
+ * demangled name without namespace and parameter list: k_ceigw_solve<true>, k_hess_down_fam<3, 2>.  Returns the bytes
+ * needed, the terminating NUL included; when buf is NULL or cap is smaller than that, nothing is written and nothing
+ * is cleared: call again with a buffer of that size.  Negative: an SMCP_E* code. */
+int64_t csp_census_read(csp_ctx* ctx, char* buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,8 @@ SIGNATURES = {
     "csp_profile_filter": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "csp_profile_read": (c_i64, [c_vp, c_vp, c_vp]),
     "csp_profile_kernel_name": (ctypes.c_char_p, [ctypes.c_int]),
+    "csp_census_enable": (ctypes.c_int, [c_vp, ctypes.c_int]),
+    "csp_census_read": (c_i64, [c_vp, c_vp, c_i64]),
     "csp_set_partition": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int]),
     "kkt_gram_prepare": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp]),
     "kkt_gram_sweep": (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, c_i64, c_vp]),

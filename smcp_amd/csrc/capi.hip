@@ -10,6 +10,9 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <string>
+#include <cxxabi.h>
+#include <cstdlib>
 #include <atomic>
 #include <thread>
 #include <type_traits>
@@ -255,20 +258,58 @@ inline bool trace_on() {
   if (t < 0) { const char* e = sw_str("SMCP_TRACE"); t = (e && e[0] == '1') ? 1 : 0; }
   return t == 1;
 }
-inline void trace_launch(int kid, dim3 grid, dim3 block, size_t lds, hipStream_t st, bool before) {
-  if (before) fprintf(stderr, "launch %s grid (%u,%u,%u) block %u lds %zu\n", KID_NAMES[kid], grid.x, grid.y, grid.z, block.x, lds);
+// The name of a kernel function from its host-side address: the device symbol as the runtime registered it, demangled and
+// cut down to the function with its template arguments (no return type, no namespace, no parameter list):
+// _ZN4smcp13k_ceigw_solveILb1EEEv... -> k_ceigw_solve<true>.  Never called on the launch path unless SMCP_TRACE=1.
+inline std::string kernel_symbol(const void* kern) {
+  const char* m = hipKernelNameRefByPtr(kern, nullptr);
+  (void)hipGetLastError();
+  return m ? std::string(m) : std::string();
+}
+inline std::string kernel_pretty(const std::string& mangled) {
+  int status = 1;
+  char* d = abi::__cxa_demangle(mangled.c_str(), nullptr, nullptr, &status);
+  std::string s = (status == 0 && d) ? std::string(d) : mangled;
+  free(d);
+  static const std::string anon = "(anonymous namespace)::";
+  for (size_t at; (at = s.find(anon)) != std::string::npos;) s.erase(at, anon.size());
+  int depth = 0;
+  size_t end = s.size();
+  for (size_t i = 0; i < s.size(); ++i) {                    // the parameter list: the first '(' outside template arguments
+    if (s[i] == '<') ++depth;
+    else if (s[i] == '>') --depth;
+    else if (s[i] == '(' && depth == 0) { end = i; break; }
+  }
+  s.resize(end);
+  depth = 0;
+  size_t begin = 0;
+  for (size_t i = 0; i < s.size(); ++i) {                    // the return type of a template and the namespaces
+    if (s[i] == '<') ++depth;
+    else if (s[i] == '>') --depth;
+    else if (depth == 0 && s[i] == ' ') begin = i + 1;
+    else if (depth == 0 && s[i] == ':' && i + 1 < s.size() && s[i + 1] == ':') begin = i + 2;
+  }
+  return s.substr(begin);
+}
+inline void trace_launch(int kid, const void* kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, bool before) {
+  if (before) fprintf(stderr, "launch %s [%s] grid (%u,%u,%u) block %u lds %zu\n", KID_NAMES[kid], kernel_pretty(kernel_symbol(kern)).c_str(),
+                      grid.x, grid.y, grid.z, block.x, lds);
   else (void)hipStreamSynchronize(st);
 }
+// a launch past the helpers that produces a result: counted, nothing else
+template <class K>
+inline void census_note(csp_ctx* c, K kern) { c->census.note((const void*)kern); }
 template <class K, class... A>
 inline void launch_lds(csp_ctx* c, int kid, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
-  if (trace_on()) trace_launch(kid, grid, block, lds, st, true);
+  if (trace_on()) trace_launch(kid, (const void*)kern, grid, block, lds, st, true);
+  c->census.note((const void*)kern);
   Profiler& P = c->prof;
   const bool timed = P.want(kid);
   if (timed) (void)hipEventRecord(P.next(), st);
   race_delay(st, false);
   hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
   note_launch(c, kid);
-  if (trace_on()) trace_launch(kid, grid, block, lds, st, false);
+  if (trace_on()) trace_launch(kid, (const void*)kern, grid, block, lds, st, false);
   if (timed) {
     (void)hipEventRecord(P.next(), st);
     P.kids.push_back(kid);
@@ -276,18 +317,7 @@ inline void launch_lds(csp_ctx* c, int kid, K kern, dim3 grid, dim3 block, size_
 }
 template <class K, class... A>
 inline void launch(csp_ctx* c, int kid, K kern, dim3 grid, dim3 block, hipStream_t st, A... args) {
-  if (trace_on()) trace_launch(kid, grid, block, 0, st, true);
-  Profiler& P = c->prof;
-  const bool timed = P.want(kid);
-  if (timed) (void)hipEventRecord(P.next(), st);
-  race_delay(st, false);
-  hipLaunchKernelGGL(kern, grid, block, 0, st, args...);
-  note_launch(c, kid);
-  if (trace_on()) trace_launch(kid, grid, block, 0, st, false);
-  if (timed) {
-    (void)hipEventRecord(P.next(), st);
-    P.kids.push_back(kid);
-  }
+  launch_lds(c, kid, kern, grid, block, 0, st, args...);
 }
 
 TreeArgs tree_args(csp_ctx* c) {
@@ -348,6 +378,7 @@ __global__ void k_latch_status(int* info, int ntrial, int* latch) {
 int fetch_info(csp_ctx* c, hipStream_t st) {
   if (c->launch_err) { c->launch_err = 0; return SMCP_EHIP; }
   if (c->lazy_status) {
+    census_note(c, k_latch_status);
     hipLaunchKernelGGL(k_latch_status, dim3(1), dim3(64), 0, st, c->D.info, (int)c->ntrial, c->D.info + 16);
     if (hipGetLastError() != hipSuccess) return SMCP_EHIP;
     c->flags_clean = true;
@@ -970,10 +1001,13 @@ __global__ void k_fingerprint_compare(unsigned long long* slots, int which, int*
 static void fp_record(csp_ctx* c, int which, const double* x, hipStream_t st) {
   if (!c->verify_cache || !c->D.fp) return;
   (void)hipMemsetAsync(c->D.fp + which, 0, sizeof(unsigned long long), st);
+  census_note(c, k_diag_fingerprint);
   hipLaunchKernelGGL(k_diag_fingerprint, dim3(1024), dim3(256), 0, st, c->D.cl, (int)c->S.nsn, x, c->D.fp + which, c->D.fp_bad, 0);
 }
 static int fp_check(csp_ctx* c, int which, const double* x, hipStream_t st) {
   if (!c->verify_cache || !c->D.fp) return 0;
+  census_note(c, k_diag_fingerprint);
+  census_note(c, k_fingerprint_compare);
   hipLaunchKernelGGL(k_diag_fingerprint, dim3(1024), dim3(256), 0, st, c->D.cl, (int)c->S.nsn, x, c->D.fp + which, c->D.fp_bad, 1);
   hipLaunchKernelGGL(k_fingerprint_compare, dim3(1), dim3(64), 0, st, c->D.fp, which, c->D.fp_bad);
   int bad = 0;
@@ -2999,6 +3033,31 @@ int csp_debug_stamps(csp_ctx* c, unsigned long long* out, int reset) {
 }
 
 const char* csp_profile_kernel_name(int kid) { return (kid >= 0 && kid < KID_COUNT) ? KID_NAMES[kid] : nullptr; }
+
+int csp_census_enable(csp_ctx* c, int on) {
+  if (!c) return SMCP_EINVAL;
+  c->census.on.store(on != 0);
+  return 0;
+}
+
+int64_t csp_census_read(csp_ctx* c, char* buf, int64_t cap) {
+  if (int rc = ready(c)) return rc;
+  HIPCHK(hipDeviceSynchronize());
+  std::lock_guard<std::mutex> g(c->census.mu);
+  std::map<std::string, int64_t> by_name;                       // sorted: the text does not depend on addresses
+  for (const auto& kv : c->census.n) {
+    std::string m = kernel_symbol(kv.first);
+    if (m.empty()) { char tmp[32]; snprintf(tmp, sizeof tmp, "?%p", kv.first); m = tmp; }
+    by_name[m] += kv.second;
+  }
+  std::string text;
+  for (const auto& kv : by_name) text += kv.first + "\t" + kernel_pretty(kv.first) + "\t" + std::to_string((long long)kv.second) + "\n";
+  const int64_t need = (int64_t)text.size() + 1;
+  if (!buf || cap < need) return need;                          // nothing is cleared: read again with a buffer of `need` bytes
+  memcpy(buf, text.c_str(), (size_t)need);
+  c->census.n.clear();
+  return need;
+}
 
 }  // extern "C"
 

@@ -2,7 +2,8 @@
 // csp_chol_update is two launches whatever the tree and whatever k: k_cu_plan (under KID_lr_apply: a workgroup per column
 // streams it once) and k_cu_walk (under KID_lr_small: one workgroup).  The walk reads the flags of k_cu_plan on the device
 // and returns at once when a column was refused, so the host waits once, for the two status words.  The workspace (flags,
-// visit bytes, then the k x n image of V that becomes w) belongs to the context.
+// visit bytes, then the k x n image of V that becomes w) belongs to the context.  The two ids are borrowed: the profile hooks
+// time the launches as k_lr_apply and k_lr_small; the launch census (csp_census_*) and SMCP_TRACE=1 name k_cu_plan and k_cu_walk.
 
 namespace {
 

@@ -2,9 +2,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <map>
+#include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "devmem.hpp"
@@ -309,6 +312,22 @@ struct Profiler {
 }  // namespace smcp
 
 namespace smcp {
+// optional launch census (csp_census_*): launches per KERNEL FUNCTION, keyed by the host-side address of the kernel as the
+// launch helpers receive it (one key per template instantiation).  Off by default: the helpers then pay one relaxed load.
+// The helpers run on several host threads in the set-up phases (hostpar.hpp), hence the lock.
+struct Census {
+  std::atomic<bool> on{false};
+  std::mutex mu;
+  std::unordered_map<const void*, int64_t> n;
+  void note(const void* kern) {
+    if (!on.load(std::memory_order_relaxed)) return;
+    std::lock_guard<std::mutex> g(mu);
+    ++n[kern];
+  }
+};
+}  // namespace smcp
+
+namespace smcp {
 struct LevelClass {
   int64_t nI = 0, nII = 0;     // cliques whose working set fits LDS / does not
   int nnmaxI = 0, namaxI = 0;  // LDS layout sizing for the LDS class
@@ -356,6 +375,7 @@ struct csp_ctx : smcp::PartitionTables {
   std::vector<smcp::LevelClass> lvl;
   smcp::DeviceCtx D;
   smcp::Profiler prof;
+  smcp::Census census;
   std::vector<int64_t> h_tmpptr;
   std::vector<int> lev_namax;   // per level: largest separator (sizes the gather launches)
   // Work that does not depend on the running leaves->root sweep and may run beside its large-front stage (the closed-form

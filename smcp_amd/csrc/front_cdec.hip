@@ -21,8 +21,8 @@
 // condition of the load; the inner dimension of column tile ct stops at min(nn, 64 (ct + 1)), beyond which Pt[j, c] is
 // zero for every j of the tile.  An element m >= n of a tile is stored in place and, for m > n, transposed: the strict
 // upper half that a diagonal tile computes is dropped, so the two triangles hold the same bits here too.
-// Both kernels are launched under borrowed kernel ids (KID_syr2k_fma, KID_syr2k_mm): SMCP_TRACE=1 and the profile hooks
-// show them as k_syr2k_fma and k_syr2k_mm.
+// Both kernels are launched under borrowed kernel ids (KID_syr2k_fma, KID_syr2k_mm): the profile hooks time them as
+// k_syr2k_fma and k_syr2k_mm; the launch census (csp_census_*) and SMCP_TRACE=1 name them k_cdec_fma and k_cdec_mm.
 #include <hip/hip_runtime.h>
 
 namespace smcp {

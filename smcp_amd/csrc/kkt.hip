@@ -839,6 +839,7 @@ int kkt_solve(csp_ctx* c, const double* L, const double* Y, const double* H, int
     if (hf && hf->on) {
       int* pinfo = c->D.info + 20;
       if (int rc = potrf_launch(c, Hw, m, ldh, hf->s, pinfo)) return rc;
+      census_note(c, k_latch_status);
       hipLaunchKernelGGL(k_latch_status, dim3(1), dim3(64), 0, hf->s, pinfo, 1, c->D.info + 16);
     } else {                                    // no side stream: where it stands, status latched as after dense_potrf
       hf.reset();

@@ -438,6 +438,7 @@ int init_gather_plan(csp_ctx* c, const InitTables& T, SetupClock& clk) {
       if (nt1) HIPCHK(hipMemcpy(D.gp_tgt, tgt.data(), sizeof(int32_t) * nt1, hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(D.gp_cptr, cptr.data(), sizeof(int64_t) * (nt1 + 1), hipMemcpyHostToDevice));
       if (ns1) HIPCHK(hipMemcpy(D.gp_src, src.data(), sizeof(int32_t) * ns1, hipMemcpyHostToDevice));
+      c->census.note((const void*)k_replicate_plan);
       hipLaunchKernelGGL(k_replicate_plan, dim3(2048), dim3(256), 0, 0, D.gp_tgt, D.gp_cptr, D.gp_src, nt1, ns1, up1, K);
       HIPCHK(hipGetLastError());
       HIPCHK(hipDeviceSynchronize());
@@ -515,6 +516,7 @@ int init_caches(csp_ctx* c) {
   if ((rc = dev_alloc(&D.fac, S.updlen(), D.mem))) return rc;
   HIPCHK(hipMemset(D.fac, 0, sizeof(double) * std::max<int64_t>(S.updlen(), 1)));     // strict upper triangles stay zero (prepare_yaa)
   if ((rc = dev_alloc(&D.sw, S.blklen(), D.mem))) return rc;
+  c->census.note((const void*)k_fill_sqrt_weights);
   hipLaunchKernelGGL(k_fill_sqrt_weights, dim3((unsigned)std::min<int64_t>(S.nsn, 4096)), dim3(256), 0, 0, D.cl, (int)S.nsn, D.sw);
   if ((rc = dev_alloc(&D.faci, S.updlen(), D.mem))) return rc;
   if ((rc = dev_alloc(&D.red, 4096, D.mem))) return rc;      // [0, 1024): reduction scratch, [1024, 4096): shares of a split Amap (kkt_solve)

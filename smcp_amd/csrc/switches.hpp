@@ -3,8 +3,9 @@
 // does not know is reported on stderr once per process (a mistyped switch would otherwise be silently ignored).  Defaults are the production
 // routes; everything else exists for A/B measurements (DESIGN.md section 3 quotes the numbers) and for the route ledger
 // (tests/route_ledger.py, tests/test_gpu_route_ledger.py), which runs every switch of the "routes" section off its default in a
-// child interpreter, against the dense definitions and with the launch counts that show the switch taking effect: a new route
-// switch must enter that ledger (a test that runs on a CPU reads this section and says so).  SMCP_BENCH_* belong to bench.py,
+// child interpreter, against the dense definitions and with the launch counts that show the switch taking effect -- per kernel id
+// (csp_profile_*) and, where an id stands for several kernels or for the arms of a template, per kernel function (csp_census_*): a
+// new route switch must enter that ledger (a test that runs on a CPU reads this section and says so).  SMCP_BENCH_* belong to bench.py,
 // SMCP_CXXFLAGS / SMCP_STAMPS to the build.
 #pragma once
 #include <cstdio>
@@ -100,7 +101,7 @@ static const Switch SWITCHES[] = {
   {"SMCP_FLOW_STAMPS", "0", "1: per-workgroup time accounts of the one-launch blocked Cholesky on stderr (waits for every launch)"},
   {"SMCP_POISON", "0", "1: every fp64 device buffer of the library (and the exchange buffers of smcp_amd/kkt.py) starts as 4.5e150 (hunting reads of never-written workspace)"},
   {"SMCP_RACE", "0", "seed > 0: delay injection on every internal stream hand-over and one launch in eight (race hunting; results must not change)"},
-  {"SMCP_TRACE", "0", "1: every launch named on stderr and waited for (a device fault points at its kernel)"},
+  {"SMCP_TRACE", "0", "1: every launch named on stderr, by its kernel id and [by the kernel function launched], and waited for (a device fault points at its kernel)"},
   {"SMCP_TIMING", "0", "1: wall-clock marks of the set-up phases on stderr"},
   {"SMCP_OCC", "0", "1: occupancy decisions of k_hess_up_n16 on stderr"},
   {"SMCP_DEBUG_ADDR", "0", "1: addresses of the large allocations on stderr"},

@@ -127,6 +127,101 @@ def random_block(n, k, pad, seed):
     return B, view, full
 
 
+def census_read(handle):
+    """{pretty kernel name: launches} since the last read of a context's launch census (csp_census_read), which it clears"""
+    from smcp_amd import _lib
+    lib = _lib.lib()
+    need = int(lib.csp_census_read(handle, None, 0))
+    while True:
+        assert need > 0, need
+        buf = ctypes.create_string_buffer(need)
+        got = int(lib.csp_census_read(handle, buf, need))
+        if got <= need:
+            break
+        need = got
+    out = {}
+    for line in buf.value.decode().splitlines():
+        _, pretty, count = line.split("\t")
+        out[pretty] = out.get(pretty, 0) + int(count)
+    return out
+
+
+def kernel_census(symb, fn):
+    """kernel FUNCTION name (k_ceigw_solve<true>: one per template instantiation) -> launches while fn() runs; launch_counts
+    gives the same launches under the kernel ids, which stand for groups of kernels"""
+    import torch
+    from smcp_amd import _lib
+    lib = _lib.lib()
+    lib.csp_census_enable(symb.handle, 1)
+    census_read(symb.handle)
+    try:
+        fn()
+        torch.cuda.synchronize()
+        return census_read(symb.handle)
+    finally:
+        lib.csp_census_enable(symb.handle, 0)
+
+
+def launch_census(symb, fn):
+    """(launch_counts, kernel_census) of ONE run of fn(): the launches under the kernel ids and under the kernel functions"""
+    box = {}
+    census = kernel_census(symb, lambda: box.update(counts=launch_counts(symb, fn)))
+    return box["counts"], census
+
+
+def pretty_kernel_name(mangled):
+    """k_hess_down_fam<3, 2> of _ZN4smcp15k_hess_down_famILi3ELi2EEEv...: the demangled name without return type, namespace and
+    parameter list (what csp_census_read writes)"""
+    import ctypes.util
+    cxx = ctypes.CDLL(ctypes.util.find_library("stdc++") or "libstdc++.so.6")
+    libc = ctypes.CDLL(None)
+    cxx.__cxa_demangle.restype = ctypes.c_void_p
+    cxx.__cxa_demangle.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+    libc.free.argtypes = [ctypes.c_void_p]
+    status = ctypes.c_int(1)
+    p = cxx.__cxa_demangle(mangled.encode(), None, None, ctypes.byref(status))
+    s = ctypes.string_at(p).decode() if status.value == 0 and p else mangled
+    if p:
+        libc.free(p)
+    s = s.replace("(anonymous namespace)::", "")
+    depth, end = 0, len(s)
+    for i, ch in enumerate(s):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif ch == "(" and depth == 0:
+            end = i
+            break
+    s, depth, begin = s[:end], 0, 0
+    for i, ch in enumerate(s):
+        if ch == "<":
+            depth += 1
+        elif ch == ">":
+            depth -= 1
+        elif depth == 0 and ch == " ":
+            begin = i + 1
+        elif depth == 0 and s[i:i + 2] == "::":
+            begin = i + 2
+    return s[begin:]
+
+
+def kernel_universe(path=None):
+    """{mangled: pretty} of every kernel instantiation the library holds: the kernel descriptors (symbols ending in .kd) of the
+    gfx950 code object inside libsmcp_amd.so, read from the file's bytes (its string tables are not compressed)"""
+    import re
+    from smcp_amd import _lib
+    with open(path or _lib.LIB_PATH, "rb") as f:
+        data = f.read()
+    names = sorted({m.group(1).decode() for m in re.finditer(rb"\x00([A-Za-z_][A-Za-z0-9_$.]*)\.kd(?=\x00)", data)})
+    return {m: pretty_kernel_name(m) for m in names}
+
+
+def kernel_function(pretty):
+    """k_hess_down_fam of k_hess_down_fam<3, 2>"""
+    return pretty.split("<")[0]
+
+
 def launch_counts(symb, fn):
     """kernel name -> launches while fn() runs (csp_profile_*: every launch of the library is counted)"""
     import torch

@@ -1,18 +1,20 @@
 """The route ledger: which checked computation launches which kernel, and which one shows each route switch taking effect.
 
 A SCENARIO is a set of switches (its `env`; empty = the default routes), an optional csp_tune setting, a list of cases and a
-SIGNATURE: the kernels that must have run (`ran`) and the ones that must not (`gone`) while the cases were measured.  A case is
+SIGNATURE: the kernel ids that must have run (`ran`) and the ones that must not (`gone`) while the cases were measured, and the
+same over the kernel FUNCTIONS (`ran_k`, `gone_k`: an id stands for a group of kernels; the launch census of csp_census_* names
+the function that was launched, one name per template instantiation).  A case is
 either a pattern with the parts of dense_ref.measure to run on it (every error is bounded by dense_ref.device_bound) or a UNIT:
 one small call of a unit outside dense_ref.measure, checked by that unit's own reference at that unit's own bound (the helper
-or test function of its GPU module is called as it stands).  Every case runs inside helpers.launch_counts.
+or test function of its GPU module is called as it stands).  Every case runs inside helpers.launch_counts and helpers.kernel_census.
 
 The switches are cached per process, so a scenario with a non-empty `env` runs in a child interpreter:
 
-    python tests/route_ledger.py <scenario> <out.json>        ->  {case: {"errors": {...}, "counts": {...}, "seconds": s}}
+    python tests/route_ledger.py <scenario> <out.json>        ->  {case: {"errors": {...}, "counts": {...}, "kernels": {...}, "seconds": s}}
 
 and the same cases run once more on the default routes, where the OPPOSITE signature must hold (a scenario whose cases never
 reach the route it claims to replace fails).  tests/test_gpu_route_ledger.py holds the tests; its docstring holds the measured
-figures.  A new kernel id or a new route switch must enter this file.
+figures.  A new kernel, a new route switch or a launch past the launch helpers must enter this file.
 """
 import contextlib
 import fnmatch
@@ -101,8 +103,9 @@ def _units():
     every kernel of the unit"""
     cap = _Capsys()
     return {
-        "trmm": [("tests.test_gpu_trmm", "check_definition", ("arrow_big", (1, 70))), ("tests.test_gpu_trmm", "check_definition", ("fam_odd", (7,)))],
-        "symm": [("tests.test_gpu_symm", "check_definition", ("arrow_big", (1, 70))), ("tests.test_gpu_symm", "check_definition", ("fam_odd", (7,)))],
+        # 1, 3 and 7 columns: the three column blocks of the FMA kernels (1, up to 4, wider; with_column_block in products.hip)
+        "trmm": [("tests.test_gpu_trmm", "check_definition", ("arrow_big", (1, 70))), ("tests.test_gpu_trmm", "check_definition", ("fam_odd", (3, 7)))],
+        "symm": [("tests.test_gpu_symm", "check_definition", ("arrow_big", (1, 70))), ("tests.test_gpu_symm", "check_definition", ("fam_odd", (3, 7)))],
         "syr2k": [("tests.test_gpu_syr2k", "check_definition", ("arrow_big", (1, 17))), ("tests.test_gpu_syr2k", "check_definition", ("fam_odd", (3,)))],
         "trmm_wide": [("tests.test_gpu_trmm", "check_definition", ("nested_mid", (70,)))],
         "syr2k_wide": [("tests.test_gpu_syr2k", "check_definition", ("nested_mid", (70,)))],
@@ -123,12 +126,45 @@ def _units():
                             ("tests.test_gpu_kkt_residual", "test_refinement_does_its_work", ())],
         "dense_potrf_potrs": [("tests.test_gpu_parity", "test_dense_potrf_potrs", (5, 0)), ("tests.test_gpu_parity", "test_dense_potrf_potrs", (130, 0)),
                               ("tests.test_gpu_parity", "test_dense_potrs_of_an_uploaded_factor", (130,))],
+        # ---- kernels of the KKT solves that the other cases do not reach: the chip-wide substitution steps of dense_potrs beyond
+        # order 1024 (k_dense_trsv_step); the panels of the stack's triangular solve beyond 320 constraints (k_stack_gemm_panel);
+        # the shifted Gram matrix of a nearly dependent stack under deferred status (k_qr_shift, k_latch_status)
+        "dense_potrs_steps": [("tests.test_gpu_parity", "test_dense_potrf_potrs", (1027, 5))],
+        "qr_panels": [("tests.test_gpu_parity", "test_kkt_qr_more_than_320_constraints", ())],
+        "qr_shifted": [("tests.test_gpu_parity", "test_kkt_qr_nearly_dependent_constraints", (1e-13, True, True))],
+        # the failure flag latched on the device (k_latch_status): a deferred solve against the eager one, and the report of a failure
+        "deferred_status": [("tests.test_gpu_parity", "test_deferred_status", ("arrow",))],
+        # the residuals alone (the refinement of residual_refine factors by QR, which the generic route does not hold)
+        "residual_rows": [("tests.test_gpu_kkt_residual", "test_rows_against_the_oracle", ("nested", 3))],
+        # ---- the units behind borrowed kernel ids (KID_ceig, KID_ceig_reduce, KID_gather_level, KID_axpby, KID_vec_axpby,
+        # KID_qr_small, KID_lr_apply, KID_lr_small, KID_syr2k_fma, KID_syr2k_mm): the census names their kernels.
+        # class_edges: both sides of every LDS class of the Jacobi kernels; fam_odd: gathers and scatters over a tree with levels
+        "clique_eigh": [("test_gpu_clique_eigh", "test_eigh_against_lapack", ("class_edges", "indefinite", cap)),
+                        ("test_gpu_clique_eigh", "test_project_against_lapack", ("class_edges", "indefinite", cap)),
+                        ("test_gpu_clique_eigh", "test_gather_and_scatter_against_dense_definitions", ("fam_odd",))],
+        "cone_project": [("test_gpu_cone_project", "test_three_iterations_against_the_restatement", ("nested", "noisy", 1.0, 1.7, cap)),
+                         ("test_gpu_cone_project", "test_three_iterations_against_the_restatement", ("class_edges", "indef", 3.0, 1.0, cap))],
+        # the chip-wide block Jacobi: orders 64 .. 161 (two to six blocks of 32 rows and the ragged last blocks): eigenvalues, vectors, projections
+        "clique_wide": [("test_gpu_clique_wide", "test_parity_and_contract", ("wide_edges", "indefinite", cap)),
+                        ("test_gpu_clique_wide", "test_block_sweeps_against_restatement", (65, "indefinite", cap))],
+        "cone_wide": [("test_gpu_cone_wide", "test_three_iterations_against_the_restatement", ("wide_root70", "indef", 1.0, 1.7, cap))],
+        "pencil_wide": [("test_gpu_pencil_wide", "parity_run", ("wide_edges",)), ("test_gpu_pencil_wide", "test_max_step_along_minus_x", ("wide_edges", cap))],
+        # dense: the smallest pattern of FULL (n = 9); random65: a tridiagonal matrix of more rows than a wave has lanes
+        "dual_step": [("test_gpu_lanczos", "test_full_krylov_both_forms", ("dense", cap)),
+                      ("test_gpu_lanczos", "test_ritz_kernel_against_eigh_tridiagonal", ("random65", cap))],
+        # ranks 1 .. 64 (17: the second, ragged pass) on a deep tree of small cliques; ranks 1 and 17 on separators beyond LDS
+        "chol_update": [("test_gpu_chol_update", "test_definition", ("band",)), ("test_gpu_chol_update", "test_definition", ("arrow_thin",))],
+        # band: the item arm alone (k_cdec_fma); arrow_big: 3 x 3 tiles in the root, the tile arm (k_cdec_mm)
+        "clique_decompose": [("test_gpu_clique_decompose", "test_definition", ("band",)), ("test_gpu_clique_decompose", "test_definition", ("arrow_big",))],
     }
 
 
 PRODUCT_UNITS = [U("trmm"), U("symm"), U("syr2k"), U("lowrank"), U("solve_many")]
 ALL_UNITS = PRODUCT_UNITS + [U("trmm_wide"), U("syr2k_wide"), U("symm_1col"), U("mrcompletion"), U("maxcut_round"), U("edmcompletion"), U("psdcompletion"), U("clique_eigvalsh"),
-                             U("solve_many_qr"), U("residual_refine"), U("dense_potrf_potrs")]
+                             U("solve_many_qr"), U("residual_refine"), U("residual_rows"), U("dense_potrf_potrs")]
+SPECTRA_UNITS = [U("clique_eigh"), U("cone_project"), U("clique_wide"), U("cone_wide"), U("pencil_wide"), U("dual_step")]
+FACTOR_UNITS = [U("chol_update"), U("clique_decompose")]
+KKT_UNITS = [U("dense_potrs_steps"), U("qr_panels"), U("qr_shifted"), U("deferred_status")]
 
 # KKT inputs of tests/test_gpu_parity.py that select a route (m, density, seed as there; tnzcols = 0: every constraint swept)
 FAM_SPARSE = [C("nested_mid", ("kkt",), m=12, density=0.002, seed=13, max_rhs=12, tnzcols=0.0),
@@ -144,20 +180,26 @@ GRAM130 = C("nested", ("kkt",), m=130, density=0.05, seed=9)      # more than on
 EVERYTHING = [C("nested_mid", ALL), C("arrow_big", ALL), C("nested_mid", ("hessian",), nrhs=4)]
 
 
-def S(env, cases, ran=(), gone=(), tune=None, note="", sig_over=None):
+def S(env, cases, ran=(), gone=(), tune=None, note="", sig_over=None, ran_k=(), gone_k=()):
     """sig_over: the signature is judged on the first sig_over cases only (the others are there for their numerics)"""
-    return dict(env=env, cases=cases, ran=list(ran), gone=list(gone), tune=tune or {}, note=note, sig_over=sig_over)
+    return dict(env=env, cases=cases, ran=list(ran), gone=list(gone), ran_k=list(ran_k), gone_k=list(gone_k), tune=tune or {}, note=note,
+                sig_over=sig_over)
 
 
 # name -> scenario.  `ran` / `gone`: kernel names (fnmatch patterns) over the union of the scenario's cases: every `ran`
 # pattern has a launch and no `gone` pattern has one; on the default routes the other way round.  The lists are what the
-# launch sites say and what both runs showed on the MI355X; `note` says where launch counts cannot show the switch.
+# launch sites say and what both runs showed on the MI355X; `ran_k` / `gone_k`: the same over the kernel functions of the
+# census (k_hess_down_w<2>: one name per instantiation); `note` says where neither count can show the switch.
 SCENARIOS = {
     # ---- the default routes: every unit outside dense_ref.measure, and the measured cases that no switch below runs
     "units": S({}, ALL_UNITS + [C("nested", ("kkt",), route="qr"), C("band", ("kkt",), route="qr")]),
     "default_small": S({}, [C(name, ALL) for name in ("band", "rand1", "rand2", "diag", "dense", "arrow")]
                        + [C("dense600", ("tree", "scaling", "hessian")), C("arrow_one", ("tree", "scaling", "hessian", "kkt")),
                           C("fam_top", ("hessian", "kkt"), nrhs=4), C("rand2", ("hessian",), nrhs=4), GRAM130]),
+    # the units that run behind borrowed kernel ids, in two children so that neither grows long
+    "units_spectra": S({}, SPECTRA_UNITS),
+    "units_factor": S({}, FACTOR_UNITS),
+    "units_kkt": S({}, KKT_UNITS),
 }
 
 
@@ -165,7 +207,8 @@ def _add(name, env, cases, **kw):
     SCENARIOS[name] = S(env, cases, **kw)
 
 
-_add("generic", {"SMCP_GENERIC": "1"}, [C("rand2", ALL), C("arrow_thin", ALL), C("nested", ("hessian", "kkt"), nrhs=4)],
+_add("generic", {"SMCP_GENERIC": "1"}, [C("rand2", ALL), C("arrow_thin", ALL), C("nested", ("hessian", "kkt"), nrhs=4), U("residual_rows")],
+     ran_k=["k_res_combine_cliques"], gone_k=["k_res_combine"],
      ran=["k_chol_level", "k_llt_level", "k_pinv_level", "k_completion_all", "k_hess_up_level", "k_hess_down_level", "k_hess_up_inv_level",
           "k_hess_down_inv_all", "k_factor_yaa", "k_scale_an"],
      gone=["k_chol_mfma<*", "k_pinv_mfma<*", "k_llt_mfma<*", "k_completion_mfma<*", "k_hess_down_mfma<*", "k_hess_up_inv_mfma<*",
@@ -187,7 +230,8 @@ _add("flow_wg5", {"SMCP_FLOW_WG": "5"}, [C("band275", ("tree", "scaling")), C("t
 _N16 = [C("nested", ("hessian", "kkt")), C("fam_odd", ("hessian", "kkt")), C("nested", ("hessian",), nrhs=4), C("fam_odd", ("hessian",), nrhs=4)]
 _add("n16_0", {"SMCP_N16": "0"}, _N16, gone=["k_hess_up_n16"], note="k_hess_up_pad runs on both routes (fam_odd's shapes beyond n16)")
 _add("oldlds1", {"SMCP_OLDLDS": "1"}, _N16, ran=["k_hess_up_mfma<true>"], gone=["k_hess_up_n16", "k_hess_up_pad"])
-_add("down_w0", {"SMCP_DOWN_W": "0"}, _N16, note="not observable: k_hess_down_w is counted under k_hess_down_mfma<true>")
+_add("down_w0", {"SMCP_DOWN_W": "0"}, _N16, gone_k=["k_hess_down_w<*"],
+     note="the id k_hess_down_mfma<true> holds k_hess_down_w<1..4> and k_hess_down_mfma<true, *>: only the census shows the switch")
 _add("fam0", {"SMCP_FAM": "0"}, [C(name, ("scaling", "hessian", "kkt"), nrhs=nrhs) for name in ("fam_odd", "fam_max", "fam_nine") for nrhs in (1, 4)],
      gone=["k_hess_up_fam", "k_hess_up_fam1", "k_hess_down_fam", "k_fam_terms", "k_famt_prep", "k_chol_fam", "k_pinv_fam", "k_leaf_*"])
 _add("fam2_0", {"SMCP_FAM2": "0"}, FAM_SPARSE, tune={"LEAFGRAM": 2}, ran=["k_hess_up_fam"], gone=["k_fam_terms", "k_famt_prep"],
@@ -202,37 +246,48 @@ _add("gram0", {"SMCP_GRAM": "0"}, [C("nested", ("kkt",)), C("arrow", ("kkt",)), 
 _add("scm0", {"SMCP_SCM": "0"}, [C("rand2", ("kkt",)), C("arrow", ("kkt",)), C("nested_mid", ("kkt",), tnzcols=0.2)],
      note="not observable: the SCMcolumn2 route is host-side bookkeeping over the same kernels")
 _add("trsm_mm0", {"SMCP_TRSM_MM": "0"}, [C("arrow_big", ("trsm",)), C("nested_mid", ("trsm",))], gone=["k_lf_prep_k", "k_prep_lk"],
-     note="the tile products themselves are not counted; what shows is the inverse-form factor they need (k_prep_lk, k_lf_prep_k); "
-          "k_trsm_*_level run on both routes (blocks of fewer than eight columns)")
+     gone_k=["k_trsm_mm_fwd", "k_trsm_mm_bwd"],
+     note="the ids show the inverse-form factor the tile products need (k_prep_lk, k_lf_prep_k), the census the tile products themselves, "
+          "which run under the ids of the level kernels; k_trsm_*_level run on both routes (blocks of fewer than eight columns)")
 _add("alds0", {"SMCP_ALDS": "0"}, [FAN_CASE, THIN_CASE, DYN_CASE], gone=["k_lf_assemble_lds", "k_lf_assemble_lds_dyn"],
      note="k_lf_assemble (the gather plan) runs on both routes: the levels below 32 pairs")
 _add("alds_dyn0", {"SMCP_ALDS_DYN": "0"}, [DYN_CASE], ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_lds_dyn"])
 _add("alds_fill0", {"SMCP_ALDS_FILL": "0"}, [FZ_CASE, THIN_CASE], tune={"LEAFGRAM": 2}, ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_fz"], sig_over=1)
-_add("asm_t", {"SMCP_ASM": "t"}, [C("arrow_big", ("hessian",), nrhs=2), THIN_CASE, C("arrow_big", ("kkt",))], ran=["k_lf_clear_upd"],
-     note="the tiled kernel is counted under k_lf_assemble like the gather plan; it shows through the clear pass it needs")
-_add("fz_tail0", {"SMCP_FZ_TAIL": "0"}, [FZ_CASE, FAN_CASE], tune={"LEAFGRAM": 2}, note="not observable: the same k_lf_assemble_fz launch without shares in its last round")
+_add("asm_t", {"SMCP_ASM": "t"}, [C("arrow_big", ("hessian",), nrhs=2), THIN_CASE, C("arrow_big", ("kkt",))], ran=["k_lf_clear_upd"], ran_k=["k_lf_assemble_tiled"],
+     note="the id k_lf_assemble holds the tiled kernel and the gather plan: the ids show the clear pass the tiled kernel needs, the census the kernel")
+_add("fz_tail0", {"SMCP_FZ_TAIL": "0"}, [FZ_CASE, FAN_CASE], tune={"LEAFGRAM": 2}, note="not observable on these cases: the same k_lf_assemble_fz launch without shares in its last round; the shares would show as k_lf_zero_pairs, "
+          "which neither case reaches (EXEMPT_KERNELS: no last round less than half full over fronts of sixteen children)")
 _add("faci_lds0", {"SMCP_FACI_LDS": "0"}, [C("nested", ("hessian", "kkt")), C("fam_max", ("hessian", "kkt"))], ran=["k_factor_inverse"], gone=["k_factor_inverse_lds"])
 _SCALING = [C("nested_mid", ("scaling", "hessian", "kkt")), C("fam_odd", ("scaling", "hessian", "kkt"))]
 _add("chol_prep0", {"SMCP_CHOL_PREP": "0"}, [C("nested_mid", ("scaling",)), C("tops8", ("scaling",)), C("fan40", ("scaling",))] + _SCALING,
      ran=["k_prep_lk"], sig_over=3,
      note="judged on the scaling point alone of trees that take its overlapped form with supernodes of at most 16 columns in the LDS class: "
           "the Hessians and the Schur sweep launch k_prep_lk on both routes")
-_add("scaling_overlap0", {"SMCP_SCALING_OVERLAP": "0"}, _SCALING, note="not observable: the same kernels one after the other")
+_add("scaling_overlap0", {"SMCP_SCALING_OVERLAP": "0"}, _SCALING, gone_k=["k_top_chol<true>", "k_chol_fam<*, true>"],
+     note="the factorisations that leave the inverse-form factor behind (k_top_chol<true>, k_chol_fam<.., true>) belong to the overlapped form; "
+          "their ids hold both arms: only the census shows the switch")
 _add("fac_partial0", {"SMCP_FAC_PARTIAL": "0"}, _SCALING, note="not observable: the same kernels, chol(Y_AA) formed at another point")
 _add("streams", {"SMCP_FORK": "0", "SMCP_NOCACHE": "1", "SMCP_POTRF_DEFER": "0"}, EVERYTHING,
      note="not observable: the same kernels on one stream, nothing reused between calls")
-_add("pd1", {"SMCP_PD": "1"}, EVERYTHING, note="not observable: the same kernels in another launch shape")
+_add("pd1", {"SMCP_PD": "1"}, EVERYTHING, ran_k=["k_lf_up1<1>", "k_lf_down1<1>", "k_lf_pinv1<1>"], gone_k=["k_lf_*<4>"],
+     note="the ids hold both launch shapes of the phase kernels of the large fronts (LAUNCH_PD: the template argument is SMCP_PD): only the census shows the switch")
 _add("gram_side", {"SMCP_GRAM_EARLY": "1", "SMCP_LG_SIDE": "0"}, EVERYTHING + FAM_SPARSE, tune={"LEAFGRAM": 2},
      note="not observable: the same kernels on other streams")
 _add("lg_early0", {"SMCP_LG_EARLY": "0"}, EVERYTHING + FAM_SPARSE, tune={"LEAFGRAM": 2}, note="not observable: the same kernels at another point of the sweep")
 _add("qr_trsm_f", {"SMCP_QR_TRSM": "f"}, [C("nested", ("kkt",), route="qr"), C("band", ("kkt",), route="qr"), C("nested_mid", ("kkt",), route="qr")],
-     note="not observable: both substitution kernels are counted under k_stack_trsm")
+     ran_k=["k_stack_trsm<*"], gone_k=["k_stack_trsm_mfma<*"],
+     note="the id k_stack_trsm holds both substitution kernels: only the census shows the switch")
 _add("products_mm0", {"SMCP_TRMM_MM": "0", "SMCP_SYR2K_MM": "0", "SMCP_SYMM_MM": "0", "SMCP_LOWRANK_MM": "0", "SMCP_POTRS_MANY_MM": "0"}, PRODUCT_UNITS,
      gone=["k_trmm_mm", "k_syr2k_mm", "k_symm_mm"],
-     note="SMCP_LOWRANK_MM and SMCP_POTRS_MANY_MM are not observable: k_lr_gram and k_potrs_many_step hold both routes")
+     gone_k=["k_trmm_mm<false>", "k_trmm_mm<true>", "k_syr2k_mm<false>", "k_syr2k_mm<true>", "k_symm_mm", "k_lr_gram<true, 1>", "k_lr_gram<true, 4>"],
+     note="every arm of the tile products is named: both directions of trmm, syr2k with and without V, both widths of lowrank's Gram "
+          "(the id k_lr_gram holds both routes); SMCP_POTRS_MANY_MM is not observable: the same kernel k_potrs_many_step holds both routes")
 _add("products_mm2", {"SMCP_TRMM_MM": "2", "SMCP_SYR2K_MM": "2", "SMCP_SYMM_MM": "2"}, [U("trmm_wide"), U("syr2k_wide"), U("symm_1col")],
-     ran=["k_trmm_n", "k_trmm_t", "k_syr2k_fma", "k_symm_mm"],
+     ran=["k_trmm_n", "k_trmm_t", "k_syr2k_fma", "k_symm_mm"], ran_k=["k_trmm_n<*", "k_trmm_t<*", "k_syr2k_fma<*", "k_symm_mm"],
      note="70 columns / ranks: the default sends every front to the tile products, value 2 the large ones only; one column: value 2 sends symm's large fronts there")
+# every reuse of a cached derived quantity is guarded by a fingerprint of the matrix it was derived from (csp_tune VERIFY_CACHE):
+# a tune alone, so the same cases run once more without it, where neither kernel is launched
+_add("verify_cache", {}, EVERYTHING, tune={"VERIFY_CACHE": 1}, ran_k=["k_diag_fingerprint", "k_fingerprint_compare"])
 
 # switch -> the module that already runs it off its default against a dense definition or a reference
 COVERED_BY = {
@@ -250,11 +305,74 @@ EXEMPT_SWITCHES = {
     "SMCP_ROOT_FUSED": "Y_NN explicit: condition squared, for studies only (switches.hpp)",
 }
 MAX_EXEMPT_SWITCHES = 6
-# kernels that are reachable, but only at an order beyond about 1100 or with more than one rank: kernel -> the launch-site condition
-EXEMPT_KERNELS = {}
+# kernels (ids or functions) that are reachable, but only at an order beyond about 1100 or with more than one rank: kernel -> the
+# launch-site condition
+EXEMPT_KERNELS = {
+    "k_exchange_roots": "kkt.hip exchange_roots: a context with a subtree partition (csp_set_partition), more than one rank",
+    "k_exchange_combine": "kkt.hip kkt_exchange_combine: a context with a subtree partition (csp_set_partition), more than one rank",
+    "k_stack_rows": "kkt.hip kkt_stack_rows: the top of the tree sharded by constraint, more than one rank",
+    "k_lf_root1": "capi.hip hess_up_fast: SMCP_ROOT_FUSED=1, a study switch (EXEMPT_SWITCHES: the condition number squared)",
+    "k_lf_root2": "capi.hip hess_down_fast: SMCP_ROOT_FUSED=1, a study switch (EXEMPT_SWITCHES: the condition number squared)",
+    "k_scatter_hd": "kkt.hip kkt_schur_gram_part: the hybrid Schur route, dense-on-V and column-sparse constraints in ONE system; "
+                    "checked on one rank only as the reference of test_column_sparse_constraints_sharded_by_constraint",
+    "k_scatter_constraints_ids": "kkt.hip kkt_schur_gram_part: the hybrid Schur route (as k_scatter_hd) without the entry lists of the sparse-input sweep",
+    "k_lf_zero_pairs": "capi.hip launch_assemble_fz: a last round less than half full of more than 256 (front, right-hand side) pairs whose fronts "
+                       "have sixteen children or more, or a sharded sweep; the cases of fz_tail0 do not reach it",
+}
 MAX_EXEMPT_KERNELS = 8
-# kernels that no input reaches: kernel -> the launch site
-DEAD_KERNELS = {}
+# kernels (ids or functions) that no input reaches: kernel -> the launch site
+DEAD_KERNELS = {
+    "k_selftest_mma": "front_mfma.hip: the self-test of the MFMA operand map has no launch site in the library",
+    "k_exchange_copy": "front_large.hip: no launch site in the library (the boundary exchange packs with k_exchange_roots)",
+}
+# the kernels launched past the launch helpers (hipLaunchKernelGGL outside launch / launch_lds), by source file: a new one fails
+# test_direct_launch_sites_are_listed.  Those that produce a result are counted by the census at their sites; csp_axpby has no
+# context, k_axpby is counted where the helpers launch it
+DIRECT_LAUNCHES = {
+    "setup.hip": ["k_fill_sqrt_weights", "k_replicate_plan"],
+    "kkt.hip": ["k_latch_status"],
+    "capi.hip": ["k_axpby", "k_diag_fingerprint", "k_fingerprint_compare", "k_latch_status", "k_probe_family_stores", "k_race_spin"],
+}
+# kernels the census does not count (at most four): kernel -> why
+NOT_COUNTED = {
+    "k_race_spin": "delay injection: a bounded spin that writes nothing, launched from inside the launch helpers",
+    "k_probe_family_stores": "csp_tune PLACEMENT: a timing probe whose stores are never read",
+}
+MAX_NOT_COUNTED = 4
+KERNEL_CENSUS_FILE = os.path.join(HERE, "golden", "kernel_census.json")
+CSRC = os.path.join(ROOT, "smcp_amd", "csrc")
+
+
+def _sources():
+    """(file name, text without // comments) of smcp_amd/csrc"""
+    for name in sorted(os.listdir(CSRC)):
+        with open(os.path.join(CSRC, name)) as f:
+            yield name, re.sub(r"//[^\n]*", "", f.read())
+
+
+def source_kernels():
+    """names of the __global__ functions of smcp_amd/csrc: the first k_* name with a parameter list behind the keyword (launch
+    bounds and attributes stand between them); a kernel of another name shows as a difference to the library's symbols"""
+    out = set()
+    for _, text in _sources():
+        out |= set(re.findall(r"__global__\b[^;{]*?\b(k_\w+)\s*\(", text))
+    return out
+
+
+def direct_launches():
+    """source file -> sorted names of the kernels at its hipLaunchKernelGGL sites, the two launch helpers (`kern`) left out"""
+    out = {}
+    for name, text in _sources():
+        found = sorted(set(re.findall(r"hipLaunchKernelGGL\(\s*([A-Za-z_]\w*)", text)) - {"kern"})
+        if found:
+            out[name] = found
+    return out
+
+
+def load_kernel_census():
+    """the instantiations that no passing scenario launches: mangled -> {"kernel": pretty, "condition": what selects it at its launch site}"""
+    with open(KERNEL_CENSUS_FILE) as f:
+        return json.load(f)
 
 
 def route_switches():
@@ -266,18 +384,24 @@ def route_switches():
 
 
 # ---- running -----------------------------------------------------------------------------------------------------------
-_CTX = {}
+_CTX, _SETUP, _UNIT_CONTEXTS = {}, {}, []
 
 
 def _context(pattern, max_rhs):
-    """(Symbolic with a device context, DenseCase) of a pattern, made once per process"""
+    """(Symbolic with a device context, DenseCase) of a pattern, made once per process; the census of its device_init is kept
+    in _SETUP for the first case that runs on it"""
     from oracle import oracle as orc
+    from smcp_amd import _lib
     from smcp_amd.symbolic import Symbolic
+    from tests.helpers import census_read
     key = (pattern, max_rhs)
     if key not in _CTX:
         pat = LEDGER_PATTERNS[pattern]()
         symb = Symbolic(pat)
+        _lib.lib().csp_census_enable(symb.handle, 1)
         symb.device_init(0, max_rhs)
+        _SETUP[key] = census_read(symb.handle)
+        _lib.lib().csp_census_enable(symb.handle, 0)
         _CTX[key] = (symb, dense_ref.DenseCase(pat, orc.Sym(symb), dense_ref.YARDSTICK_SEED))
     return _CTX[key]
 
@@ -303,9 +427,10 @@ def _scaling_errors(symb, case):
 
 def run_measured(case_, tune):
     from smcp_amd import chordal
-    from tests.helpers import launch_counts
+    from tests.helpers import kernel_census, launch_counts
     _, pattern, parts, nrhs, kkt = case_
     symb, case = _context(pattern, max(4, kkt["max_rhs"], nrhs))
+    kernels = _SETUP.pop((pattern, max(4, kkt["max_rhs"], nrhs)), {})
     set_recipe(case, kkt)
     errs = {}
 
@@ -321,38 +446,50 @@ def run_measured(case_, tune):
 
     for what, value in tune.items():
         chordal.tune(symb, getattr(chordal, "TUNE_" + what), value)
+    box = {}
     try:
-        counts = launch_counts(symb, run)
+        for k, v in kernel_census(symb, lambda: box.update(counts=launch_counts(symb, run))).items():
+            kernels[k] = kernels.get(k, 0) + v
     finally:
         for what in tune:
             chordal.tune(symb, getattr(chordal, "TUNE_" + what), 1 if what == "LEAFGRAM" else 0)
-    return errs, counts
+    return errs, box["counts"], kernels
 
 
 def run_unit(unit):
-    """the unit's own checks (they assert), with the launches of every context they make counted"""
+    """the unit's own checks (they assert), with the launches of every context they make counted, those of its device_init included"""
     import ctypes
     import importlib
     import torch
     from smcp_amd import _lib
     from smcp_amd.symbolic import Symbolic
+    from tests.helpers import census_read
     lib = _lib.lib()
     nk = int(lib.csp_profile_kinds())
     names = [lib.csp_profile_kernel_name(i).decode() for i in range(nk)]
-    made = []
+    made = _UNIT_CONTEXTS           # the modules keep their contexts: a later unit of the process may run on one an earlier unit made
     plain = Symbolic.device_init
 
+    def switch_on(s):
+        lib.csp_profile_filter(s.handle, -1)
+        lib.csp_profile_enable(s.handle, 1)
+        lib.csp_profile_read(s.handle, None, None)
+
     def counted(self, *a, **k):
+        lib.csp_census_enable(self.handle, 1)
         out = plain(self, *a, **k)
         if not any(s is self for s in made):
             made.append(self)
-            lib.csp_profile_filter(self.handle, -1)
-            lib.csp_profile_enable(self.handle, 1)
-            lib.csp_profile_read(self.handle, None, None)
+            switch_on(self)
         return out
 
+    for s in made:
+        switch_on(s)
+        lib.csp_census_enable(s.handle, 1)
+        census_read(s.handle)
+
     from smcp_amd import solvers
-    counts = {}
+    counts, kernels = {}, {}
     Symbolic.device_init = counted
     peo = solvers.options.get("peo", "auto")
     solvers.options["peo"] = "mcs"                    # as tests/conftest.py pins it for every test
@@ -370,7 +507,10 @@ def run_unit(unit):
             for i in range(nk):
                 if cnt[i]:
                     counts[names[i]] = counts.get(names[i], 0) + int(cnt[i])
-    return {}, counts
+            for k, v in census_read(s.handle).items():
+                kernels[k] = kernels.get(k, 0) + v
+            lib.csp_census_enable(s.handle, 0)
+    return {}, counts, kernels
 
 
 def run_cases(cases, tune):
@@ -379,10 +519,10 @@ def run_cases(cases, tune):
     for case_ in cases:
         t0 = time.perf_counter()
         try:
-            errs, counts = run_unit(case_[1]) if case_[0] == "unit" else run_measured(case_, tune)
-            out[case_key(case_)] = {"errors": errs, "counts": counts, "seconds": time.perf_counter() - t0}
+            errs, counts, kernels = run_unit(case_[1]) if case_[0] == "unit" else run_measured(case_, tune)
+            out[case_key(case_)] = {"errors": errs, "counts": counts, "kernels": kernels, "seconds": time.perf_counter() - t0}
         except Exception:
-            out[case_key(case_)] = {"errors": {}, "counts": {}, "seconds": time.perf_counter() - t0, "failed": traceback.format_exc()[-3000:]}
+            out[case_key(case_)] = {"errors": {}, "counts": {}, "kernels": {}, "seconds": time.perf_counter() - t0, "failed": traceback.format_exc()[-3000:]}
             break
     return out
 
@@ -444,6 +584,8 @@ def collect(timeouts, tmpdir, log=lambda *a: None):
             t0 = time.perf_counter()
             rec["run"] = default_run(scn)
             rec["seconds"] = time.perf_counter() - t0
+            if scn["tune"]:                                          # a tune alone: the same cases once more without it
+                rec["default"] = default_run(dict(scn, tune={}))
         else:
             rec["run"], rec["rc"], rec["seconds"], rec["tail"] = run_child(name, scn["env"], timeouts.get(name, CHILD_SECONDS), tmpdir)
             if rec["rc"] == "timeout" or rec["rc"] < 0:
@@ -456,10 +598,11 @@ def collect(timeouts, tmpdir, log=lambda *a: None):
 
 
 # ---- judging -----------------------------------------------------------------------------------------------------------
-def union_counts(results):
+def union_counts(results, what="counts"):
+    """what: "counts" (launches per kernel id) or "kernels" (per kernel function: the census)"""
     tot = {}
     for r in results.values():
-        for k, v in r["counts"].items():
+        for k, v in r.get(what, {}).items():
             tot[k] = tot.get(k, 0) + v
     return tot
 

@@ -29,7 +29,7 @@ from smcp_amd import _lib, chordal
 from smcp_amd.cspmatrix import _stream, cspmatrix
 from smcp_amd.symbolic import Symbolic
 from tests import chol_update_ref as R
-from tests.helpers import EXTRA, GPU_PATTERNS, launch_counts, padded
+from tests.helpers import EXTRA, GPU_PATTERNS, launch_census, padded
 from tests.trmm_ref import factor_input
 
 pytestmark = pytest.mark.gpu
@@ -287,7 +287,8 @@ def test_launches():
             Vd = torch.from_numpy(np.ascontiguousarray(V.T)).cuda()
             chordal.chol_update(cspmatrix(symb, blk.clone()), Vd, a)             # (the workspace is grown outside the count)
             L = cspmatrix(symb, blk.clone())
-            counts[name, k] = launch_counts(symb, lambda: chordal.chol_update(L, Vd, a))
-            print(name, k, counts[name, k])
+            counts[name, k], census = launch_census(symb, lambda: chordal.chol_update(L, Vd, a))
+            print(name, k, counts[name, k], census)
             assert counts[name, k] == {"k_lr_apply": 1, "k_lr_small": 1}
+            assert census == {"k_cu_plan": 1, "k_cu_walk": 1}                    # the kernels behind the two ids
     assert len({tuple(sorted(c.items())) for c in counts.values()}) == 1

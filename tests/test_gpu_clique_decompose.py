@@ -18,7 +18,7 @@ from smcp_amd.cspmatrix import _stream, cspmatrix
 from smcp_amd.symbolic import Symbolic
 from tests import clique_decompose_ref as R
 from tests import syr2k_ref
-from tests.helpers import EXTRA, GPU_PATTERNS, PATTERNS, launch_counts
+from tests.helpers import EXTRA, GPU_PATTERNS, PATTERNS, launch_census, launch_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -173,23 +173,26 @@ def test_duality(name):
 
 def test_launches():
     """one or two launches whatever the tree, under the borrowed kernel names: the deep band counts what the single clique
-    counts"""
+    counts; the launch census names the kernels behind the ids, k_cdec_fma (items) and k_cdec_mm (tiles)"""
     for name in ("band", "dense"):
         c = case(name)
         run(name, 0)                                                  # (the plan is built outside the count)
         assert launch_counts(c.symb, lambda: chordal.clique_decompose(c.L)) == {"k_syr2k_fma": 1}
+        assert launch_census(c.symb, lambda: chordal.clique_decompose(c.L))[1] == {"k_cdec_fma": 1}
     c = case("arrow_big")
     run("arrow_big", 0)
-    counts = launch_counts(c.symb, lambda: chordal.clique_decompose(c.L))
-    print("arrow_big", counts)
+    counts, census = launch_census(c.symb, lambda: chordal.clique_decompose(c.L))
+    print("arrow_big", counts, census)
     assert counts.get("k_syr2k_mm", 0) == 1 and counts.get("k_syr2k_fma", 0) <= 1 and set(counts) <= {"k_syr2k_mm", "k_syr2k_fma"}
+    assert census.get("k_cdec_mm", 0) == 1 and census.get("k_cdec_fma", 0) == counts.get("k_syr2k_fma", 0) and set(census) <= {"k_cdec_mm", "k_cdec_fma"}
     chordal.tune(c.symb, chordal.TUNE_DETERMINISTIC, 1)
     try:
-        counts = launch_counts(c.symb, lambda: chordal.clique_decompose(c.L))
+        counts, census = launch_census(c.symb, lambda: chordal.clique_decompose(c.L))
     finally:
         chordal.tune(c.symb, chordal.TUNE_DETERMINISTIC, 0)
-    print("arrow_big deterministic", counts)
+    print("arrow_big deterministic", counts, census)
     assert counts == {"k_syr2k_fma": 1}
+    assert census == {"k_cdec_fma": 1}
 
 
 @pytest.mark.parametrize("name", ["band", "two_components", "arrow_thin", "arrow_big", "three_tops"])

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import PATTERNS, launch_counts
+from helpers import PATTERNS, launch_census
 from smcp_amd import _lib, chordal, problems
 from smcp_amd.symbolic import Symbolic
 from test_clique_eig_host import EPS, clique_blocks
@@ -272,13 +272,20 @@ def test_launch_counts(name):
     Z = chordal.clique_gather(X)
     chordal.clique_eigh(X), chordal.clique_project(X), chordal.clique_scatter(symb, Z)       # buffers of the first calls
     for fn in (lambda: chordal.clique_eigh(X), lambda: chordal.clique_project(X, -0.5, 0.5, return_info=True)):
-        counts = launch_counts(symb, fn)
+        counts, census = launch_census(symb, fn)
         assert 1 <= counts["k_ceig"] <= 6 and counts["k_ceig_reduce"] == 1
         assert set(counts) <= {"k_ceig", "k_ceig_reduce", "k_gather_level"}  # only the gathers grow with the depth of the tree
         assert counts.get("k_gather_level", 0) <= symb.nlev
-    assert launch_counts(symb, lambda: chordal.clique_scatter(symb, Z)) == {"k_gather_level": symb.nlev}
-    counts = launch_counts(symb, lambda: chordal.clique_gather(X))
+        # the kernels behind the ids: the Jacobi kernel with eigenvectors, one launch per LDS class in use, and the gathers
+        assert census.get("k_ceig_vec", 0) == counts["k_ceig"] and census["k_ceig_reduce"] == 1, census
+        assert census.get("k_gather_level", 0) == counts.get("k_gather_level", 0), census
+        assert set(census) <= {"k_ceig_vec", "k_ceig_reduce", "k_gather_level"}, census
+    counts, census = launch_census(symb, lambda: chordal.clique_scatter(symb, Z))
+    assert counts == {"k_gather_level": symb.nlev} and census == {"k_clique_scatter": symb.nlev}, census
+    counts, census = launch_census(symb, lambda: chordal.clique_gather(X))
     assert set(counts) == {"k_gather_level"} and counts["k_gather_level"] <= symb.nlev + 1
+    assert census.get("k_clique_gather", 0) >= 1 and sum(census.values()) == counts["k_gather_level"], census
+    assert set(census) <= {"k_clique_gather", "k_gather_level"}, census
 
 
 def test_device_bytes_grow_on_the_first_call_only():

@@ -10,7 +10,7 @@ import scipy.sparse as sp
 import torch
 
 import smcp_amd
-from helpers import EXTRA, launch_counts
+from helpers import EXTRA, launch_census
 from smcp_amd import _lib, chordal
 from smcp_amd.cspmatrix import cspmatrix
 from smcp_amd.symbolic import Symbolic
@@ -316,7 +316,12 @@ def test_launch_chain():
     a, x, U, W = start(symb, cone_input(symb, "noisy"))
     hist = torch.zeros((9, 4), dtype=torch.float64, device="cuda")
     run_steps(symb, a, x, U, W, 1.0, 1.7, 0, 1, hist)                         # the workspace of the first call
-    counts = launch_counts(symb, lambda: run_steps(symb, a, x, U, W, 1.0, 1.7, 1, 8, hist))
+    counts, census = launch_census(symb, lambda: run_steps(symb, a, x, U, W, 1.0, 1.7, 1, 8, hist))
     assert counts["k_ceig_reduce"] == 8 and counts["k_axpby"] == 8 and 8 <= counts["k_ceig"] <= 48
     assert counts["k_gather_level"] <= 8 * (2 * symb.nlev + 1)
     assert set(counts) == {"k_ceig_reduce", "k_axpby", "k_ceig", "k_gather_level"}
+    # the kernels behind the four ids, per iteration: the gather of x, k_cone_split per slot class, the scatter of W per level,
+    # k_cone_update, k_cone_resid
+    assert census["k_cone_resid"] == 8 and census["k_cone_update"] == 8 and census["k_cone_split"] == counts["k_ceig"], census
+    assert census["k_clique_scatter"] == 8 * symb.nlev and census["k_gather_level"] == counts["k_gather_level"] - 8 * symb.nlev, census
+    assert set(census) == {"k_cone_resid", "k_cone_update", "k_cone_split", "k_clique_scatter", "k_gather_level"}, census

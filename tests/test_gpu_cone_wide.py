@@ -13,7 +13,7 @@ import scipy.sparse as sp
 import torch
 
 import smcp_amd
-from helpers import GPU_PATTERNS, PATTERNS, launch_counts
+from helpers import GPU_PATTERNS, PATTERNS, launch_census, launch_counts
 from smcp_amd import chordal
 from smcp_amd.symbolic import Symbolic
 from test_clique_eigh_host import lower_slots, unpack
@@ -176,6 +176,13 @@ def test_launch_chain_does_not_depend_on_the_data():
     assert counts["indef", 1]["k_ceig_reduce"] == 31 + 1, counts["indef", 1]
     assert counts["indef", 1]["k_ceig"] == 2 + 30 * 6 + 3 + 1, counts["indef", 1]
     assert counts["indef", 1]["k_axpby"] == 1, counts["indef", 1]
+    # the kernels behind the ids, one iteration: the chain of cone_wide_pass for the one wide clique, k_cone_split for the leaves
+    a, x, U, W = start(symb, cone_input(symb, "indef"))
+    _, census = launch_census(symb, lambda: run_steps(symb, a, x, U, W, 1.0, 1.7, 0, 1, hist))
+    chain = {"k_ceigw_cone_form": 1, "k_ceigw_begin": 1, "k_ceigw_check": 31, "k_ceigw_pivot": 90, "k_ceigw_apply": 90, "k_ceigw_sort": 1,
+             "k_ceigw_cone_split": 1, "k_ceigw_cone_finish": 1, "k_cone_split": 1, "k_cone_update": 1, "k_cone_resid": 1}
+    assert {k: census.get(k, 0) for k in chain} == chain, census
+    assert set(census) - set(chain) <= {"k_clique_scatter", "k_gather_level"} and census["k_clique_scatter"] == symb.nlev, census
 
 
 # ---- 4. the whole call -----------------------------------------------------------------------------------------------------------

@@ -18,7 +18,7 @@ import pytest
 import scipy.sparse as sp
 import torch
 
-from helpers import GPU_PATTERNS, launch_counts, padded
+from helpers import GPU_PATTERNS, launch_census, launch_counts, padded
 from smcp_amd import _lib, base, chordal, problems
 from smcp_amd.cspmatrix import _stream, cspmatrix
 from smcp_amd.symbolic import Symbolic
@@ -308,6 +308,14 @@ def test_launch_counts(pencil):
     assert ("k_symm_combine" in one) == pencil
     first = launch_counts(symb, lambda: lib.csp_lanczos_steps(h, Lp, Dp, wp, jmax, 0, 1, _stream()))
     assert first["k_vec_axpby"] == 7 + 3                                 # the start vector is normalised at j0 = 0
+    # the kernels behind k_vec_axpby and k_qr_small, by name (the launch census)
+    lz = lambda census: {k: v for k, v in census.items() if k.startswith("k_lz_")}
+    counts, census = launch_census(symb, lambda: lib.csp_lanczos_steps(h, Lp, Dp, wp, jmax, 8, 1, _stream()))
+    assert counts == one and lz(census) == {"k_lz_copy": 1, "k_lz_dots": 2, "k_lz_update": 2, "k_lz_finish": 1, "k_lz_scale": 1}, census
+    assert "k_vec_axpby" not in census and "k_vec_axpby_parts" not in census, census
+    assert launch_census(symb, lambda: lib.csp_lanczos_ritz(h, wp, jmax, _stream()))[1] == {"k_lz_ritz": 1}
+    census = launch_census(symb, lambda: lib.csp_lanczos_steps(h, Lp, Dp, wp, jmax, 0, 1, _stream()))[1]
+    assert sum(lz(census).values()) == 7 + 3 and set(lz(census)) == {"k_lz_copy", "k_lz_dots", "k_lz_update", "k_lz_finish", "k_lz_scale"}, census
 
 
 # ---- the scipy forms -----------------------------------------------------------------------------------------------------

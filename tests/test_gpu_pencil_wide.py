@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import launch_counts
+from helpers import launch_census
 from smcp_amd import _lib, chordal
 from smcp_amd.symbolic import Symbolic
 from test_clique_eig_host import EPS, clique_blocks, clique_spectra_ref, inputs, max_step_ref, pencil_B_on_V
@@ -351,6 +351,17 @@ def chain(symb, block_sweeps, narrow_launches):
     return block_sweeps + 2, narrow_launches + 1 + (3 * nt + 1) + 1 + 2 * steps * block_sweeps + 1
 
 
+def chain_kernels(symb, block_sweeps):
+    """the same chain by kernel function (the launch census): what wide_pass of csrc/completions.hip launches for a pencil"""
+    nfmax = int(orders(symb).max())
+    nb, nt = -(-nfmax // CW_B), -(-nfmax // CW_T)
+    steps = nb + (nb & 1) - 1
+    return {"k_ceigw_form": 1, "k_ceigw_potrf": nt, "k_ceigw_panel": nt - 1, "k_ceigw_trail": nt - 1, "k_ceigw_solve<true>": 1,
+            "k_ceigw_solve<false>": 1, "k_ceigw_symm": 1, "k_ceigw_begin": 1, "k_ceigw_check": block_sweeps + 1,
+            "k_ceigw_pivot": steps * block_sweeps, "k_ceigw_apply": steps * block_sweeps, "k_ceigw_sort": 1, "k_ceig_reduce": 1,
+            "k_ceigw_out": 0}
+
+
 @pytest.mark.parametrize("name,narrow", [("129", 0), ("wide_edges", 1)])
 def test_launch_chain_depends_on_the_pattern_and_the_block_sweeps_alone(name, narrow):
     symb = device_symb(name)
@@ -364,11 +375,17 @@ def test_launch_chain_depends_on_the_pattern_and_the_block_sweeps_alone(name, na
         for kind, A, Bk in (("indefinite", on_device(symb, blkS), B), ("A = B", B, B), ("B not pd", on_device(symb, blkS), on_device(symb, bad))):
             call = lambda: raised_by(lambda: chordal.clique_eigvalsh(A, Bk))
             call()                                                           # buffers of the first call
-            counts = launch_counts(symb, call)
+            counts, census[kind] = launch_census(symb, call)
             got[kind] = (counts.get("k_ceig_reduce", 0), counts.get("k_ceig", 0), chordal.clique_eig_sweeps(symb))
         return got
 
+    census = {}
     got = tuned(symb, run)
+    for kind, (n_reduce, n_ceig, sweeps) in got.items():                        # the kernels behind the two ids, by name
+        want = chain_kernels(symb, n_reduce - 2)
+        assert {k: census[kind].get(k, 0) for k in want} == want, "%s %s: %s, chain %s" % (name, kind, census[kind], want)
+        rest = {k: v for k, v in census[kind].items() if k not in want and k != "k_gather_level"}      # (the gathers of A and B: an id of their own)
+        assert rest == ({"k_ceig": narrow} if narrow else {}), "%s %s: beside the chain %s" % (name, kind, rest)
     for kind, (n_reduce, n_ceig, sweeps) in got.items():
         block_sweeps = n_reduce - 2                                          # the checks read back, but for the last
         assert 0 <= block_sweeps <= 30
