@@ -36,6 +36,112 @@ BOUND_CAP = 1e-12
 # the suite's KKT input recipe
 # (seed 9, as tests/test_gpu_parity.py: on `diag` every constraint is a single entry, and these seven are distinct)
 KKT_M, KKT_DENSITY, KKT_KK, KKT_SEED = 7, 0.05, (1.0, 0.25), 9
+# the mixed recipe: entries of the two narrow kinds of constraint (a constraint of k entries touches at most 2 k rows / columns)
+FEW_ENTRIES, SINGLE_ENTRIES = 3, 1
+MIX_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "hybrid_recipe_yardstick.json")
+
+
+# ---- the mixed KKT recipe ----------------------------------------------------------------------------------------------
+def interleave(nwide, nfew, nsingle):
+    """the order of a mixed recipe as a string over 'f' (few), 'w' (wide), 's' (single): the kinds dealt in turn
+    (f, w, s, f, w, s, ...) until each has run out, so that neither class of the device is a contiguous range"""
+    left, out = {"f": nfew, "w": nwide, "s": nsingle}, []
+    while any(left.values()):
+        for kind in "fws":
+            if left[kind]:
+                left[kind] -= 1
+                out.append(kind)
+    return "".join(out)
+
+
+def mixed_constraints(lay, m, density, seed, mix):
+    """(cptr, cidx, cval) of len(mix) constraints in the order `mix`: its 'w' constraints are random_constraints(lay, m, density,
+    seed) unchanged and in their order (mix holds m of them), an 'f' has FEW_ENTRIES entries and an 's' one entry, at V slots
+    drawn without replacement over all narrow constraints together (so no two of them are multiples of each other)"""
+    assert set(mix) <= set("fws") and mix.count("w") == m, (mix, m)
+    wptr, widx, wval = problems.random_constraints(lay, m, density=density, seed=seed) if m else (np.zeros(1, np.int64), np.zeros(0, np.int64), np.zeros(0))
+    rng = np.random.default_rng(seed + 1000)
+    need = FEW_ENTRIES * mix.count("f") + SINGLE_ENTRIES * mix.count("s")
+    slots = rng.choice(problems.lower_positions(lay), size=need, replace=False)
+    # values bounded away from zero and scaled so that a narrow constraint has about the Frobenius norm of a wide one (per: the
+    # entries of a wide one, each standard normal): H is then not badly scaled by construction -- a single entry of 0.005 beside
+    # hundreds of order one put cond(H) at 2e6 on nested_mid and the ORACLE's kkt_y at 5e-14, which says nothing about any route
+    vals = rng.standard_normal(need)
+    vals = np.sign(vals) * (0.5 + np.abs(vals))
+    per = max(1, int(wptr[1])) if m else 1
+    idx, val, ptr, w, t = [], [], [0], 0, 0
+    for kind in mix:
+        if kind == "w":
+            i, v = widx[wptr[w]:wptr[w + 1]], wval[wptr[w]:wptr[w + 1]]
+            w += 1
+        else:
+            k = FEW_ENTRIES if kind == "f" else SINGLE_ENTRIES
+            order = np.argsort(slots[t:t + k])
+            i, v = slots[t:t + k][order], vals[t:t + k][order] * np.sqrt(per / k)
+            t += k
+        idx.append(i)
+        val.append(v)
+        ptr.append(ptr[-1] + len(i))
+    return np.array(ptr, dtype=np.int64), np.concatenate(idx).astype(np.int64), np.concatenate(val)
+
+
+def touched(S, con):
+    """per constraint, the number of distinct rows / columns (permuted coordinates) its entries touch: what the device's
+    classification compares with int(n * tnzcols)"""
+    cptr, cidx, cval = con
+    out = []
+    for j in range(len(cptr) - 1):
+        u = np.zeros(S.blklen)
+        u[cidx[cptr[j]:cptr[j + 1]]] = 1.0
+        r, c = np.nonzero(S.dense(u))
+        out.append(len(set(r.tolist()) | set(c.tolist())))
+    return out
+
+
+def hybrid_case(pattern, m, density, seed, mix, tnzcols, max_rhs=None):
+    """a hybrid case: the mixed recipe (m wide ones at `density`, order `mix`) on a pattern, the tnzcols that must separate its
+    wide constraints (swept) from its narrow ones (column-sparse), and the max_rhs of the context (default: all wide ones in one block)"""
+    return dict(pattern=pattern, recipe=(m, density, seed, mix), tnzcols=tnzcols, max_rhs=max_rhs or max(4, m))
+
+
+_NESTED = ("nested", 5, KKT_DENSITY, KKT_SEED)
+# name -> hybrid case of tests/test_gpu_hybrid_schur.py.  The seven patterns with 4 few + 3 single constraints dealt among the wide
+# ones (`diag` has no wide class); then the class-size edges on `nested`; then many single-entry constraints (chunks)
+HYBRID_CASES = {
+    "nested": hybrid_case(*_NESTED, interleave(5, 4, 3), 0.2),
+    "rand2": hybrid_case("rand2", 5, KKT_DENSITY, KKT_SEED, interleave(5, 4, 3), 0.2),
+    "arrow": hybrid_case("arrow", 5, KKT_DENSITY, KKT_SEED, interleave(5, 4, 3), 0.25),
+    "fam_odd": hybrid_case("fam_odd", 6, 0.03, 13, interleave(6, 4, 3), 0.1),
+    "nested_mid": hybrid_case("nested_mid", 12, 0.002, 13, interleave(12, 4, 3), 0.1),
+    "arrow_big": hybrid_case("arrow_big", 4, 0.004, 52, interleave(4, 4, 3), 0.1),
+    "arrow_thin": hybrid_case("arrow_thin", 8, 0.03, 32, interleave(8, 4, 3), 0.1),
+    "md1": hybrid_case("nested", 1, KKT_DENSITY, KKT_SEED, interleave(1, 3, 2), 0.2),                   # one swept, five sparse
+    "ns1": hybrid_case("nested", 5, KKT_DENSITY, KKT_SEED, interleave(5, 0, 1), 0.2),                   # five swept, one sparse
+    "two_blocks": hybrid_case(*_NESTED, interleave(5, 4, 3), 0.2, max_rhs=4),                         # five swept in blocks of 4 + 1 into one D.hd
+    "gram130": hybrid_case("nested", 130, KKT_DENSITY, KKT_SEED, interleave(130, 2, 1), 0.2, max_rhs=4),   # md > GRAM_BLK = 128
+    "ends": hybrid_case("nested", 5, KKT_DENSITY, KKT_SEED, "w" + interleave(3, 4, 3) + "w", 0.2),       # swept at index 0 and at index m - 1
+    # two chunks of sparse constraints: fam_odd has the smallest trsm_cap per right-hand side of the seven patterns (29), so with
+    # max_rhs = 4 the 70 single-entry constraints (one or two columns of the inverse each) pass vcols = trsm_cap = 117 columns
+    "chunks": hybrid_case("fam_odd", 2, 0.03, 13, interleave(2, 0, 70), 0.1, max_rhs=4),
+}
+
+
+def recipe_key(pattern, recipe):
+    m, density, seed, mix = recipe
+    return "%s|m=%d,density=%s,seed=%d,mix=%s" % (pattern, m, density, seed, mix)
+
+
+def load_mix_yardstick():
+    with open(MIX_FILE) as f:
+        return json.load(f)
+
+
+def hybrid_bound(key, op, yard=None, own=None):
+    """bound of a device-vs-dense check on a mixed recipe: 100 x the larger of the global yardstick value and the recorded
+    oracle-vs-dense error of this (pattern, recipe) (tests/golden/hybrid_recipe_yardstick.json), never looser than BOUND_CAP"""
+    yard = load_yardstick() if yard is None else yard
+    own = load_mix_yardstick() if own is None else own
+    return min(100.0 * max(float(yard[op]["value"]), float(own[key][op])), BOUND_CAP)
 
 
 # ---- layout helpers ----------------------------------------------------------------------------------------------------
@@ -111,7 +217,8 @@ class DenseCase:
         self.Ablk = S.project(self.proj(self.A))
         self.Yblk = S.project(self.proj(self.Ai))
         self._kkt = None
-        self.kkt_recipe = (KKT_M, KKT_DENSITY, KKT_SEED)    # (m, density, seed); tests/route_ledger.py sets its own before kkt()
+        # (m, density, seed) or, mixed, (wide ones, density, seed, order: interleave); tests/route_ledger.py sets its own before kkt()
+        self.kkt_recipe = (KKT_M, KKT_DENSITY, KKT_SEED)
 
     def proj(self, M):
         return np.where(self.mask, M, 0.0)
@@ -144,8 +251,12 @@ class DenseCase:
     def kkt(self):
         if self._kkt is None:
             S = self.S
-            m, density, seed = self.kkt_recipe
-            cptr, cidx, cval = problems.random_constraints(self.lay, m, density=density, seed=seed)
+            m, density, seed = self.kkt_recipe[:3]
+            mix = self.kkt_recipe[3] if len(self.kkt_recipe) > 3 else None
+            if mix:                                          # (m: the wide ones; the definitions below do not know about kinds)
+                cptr, cidx, cval = mixed_constraints(self.lay, m, density, seed, mix)
+            else:
+                cptr, cidx, cval = problems.random_constraints(self.lay, m, density=density, seed=seed)
             K = orc.KKT(S, cptr, cidx, cval)
             Ad = [S.dense(K.constraint(j)) for j in range(K.m)]
             W = [self.Ai @ Aj @ self.Ai for Aj in Ad]
@@ -320,14 +431,26 @@ def to_host(X):
     return X.blkval.cpu().numpy()
 
 
-def device_kkt(symb, route="chol", tnzcols=None, max_rhs=4):
+def constraint_classes(sysk):
+    """(swept through the Hessian, column-sparse) as the device classified the constraints of a KKTSystem (kkt_constraint_classes)"""
+    import ctypes
+    from smcp_amd import _lib
+    cnt = (ctypes.c_int64 * 2)()
+    assert _lib.lib().kkt_constraint_classes(sysk.symb.handle, cnt) == 0
+    return int(cnt[0]), int(cnt[1])
+
+
+def device_kkt(symb, route="chol", tnzcols=None, max_rhs=4, classes=None):
     """kkt(con, l, y) of `measure` on the device: route 'chol' (KKTSystem.factor) or 'qr' (factor_qr, tnzcols = 0).
-    The last system built is kept in device_kkt.last (the contract tests look at its aadj)."""
+    The last system built is kept in kkt.last (the contract tests look at its aadj), its classes in kkt.classes; `classes`:
+    the (swept, sparse) counts the caller expects -- another classification fails here instead of passing on another route."""
     import torch
     from smcp_amd.kkt import KKTSystem
 
     def kkt(con, l, y):
         sysk = KKTSystem(symb, *con, max_rhs=max_rhs, tnzcols=0.0 if route == "qr" else tnzcols)
+        kkt.classes = constraint_classes(sysk)
+        assert classes is None or kkt.classes == tuple(classes), "constraint classes (swept, sparse) %s, expected %s" % (kkt.classes, tuple(classes))
         Ld, Yd = to_dev(symb, l), to_dev(symb, y)
         if route == "qr":
             solve_ = sysk.factor_qr(Ld, Yd)

@@ -63,17 +63,25 @@ NEW_PATTERNS = {
     "tops8": lambda: problems.nested_block_arrow_pattern(nsub=8, nmid=2, nleaf_per_mid=2, seed=5),
     # nine family parents that share one separator (test_kkt_family_sibling_groups_send_one_summed_update): groups of 8 + 1
     "fam_shared": lambda: problems.nested_block_arrow_pattern(nsub=1, nmid=9, nleaf_per_mid=3, seed=71, shared_mid_sep=True),
+    # eight large fronts (nf = 130: beyond the LDS class, within the streaming extend-add) in one level, sixteen family parents under
+    # each: with 40 sparse-input right-hand sides 40 queues of eight (front, right-hand side) pairs on 32 queues of workgroups, so
+    # the last round holds eight queues of 32 and is dealt in shares of the pairs' children (launch_assemble_fz: tail_first = 32, nzt = 2)
+    "tail8": lambda: problems.nested_block_arrow_pattern(nsub=8, nmid=16, nleaf_per_mid=2, leaf=(2, 9), mid=(4, 20), top=(30, 100), root=110),
+    # ONE such front with 32 family parents under it: with 20 right-hand sides 20 pairs, fewer than half the CUs, each with 32 children:
+    # alds_route deals the children of every pair over two workgroups (launch_assemble_fz: tail_first = 0, every pair shared)
+    "fan32": lambda: problems.nested_block_arrow_pattern(nsub=1, nmid=32, nleaf_per_mid=2, leaf=(2, 9), mid=(4, 20), top=(30, 100), root=110),
 }
 LEDGER_PATTERNS = dict(GPU_PATTERNS)
 LEDGER_PATTERNS.update(NEW_PATTERNS)
 
 
 # ---- cases -------------------------------------------------------------------------------------------------------------
-def C(pattern, parts, nrhs=1, m=None, density=None, seed=None, max_rhs=4, tnzcols=None, route="chol"):
+def C(pattern, parts, nrhs=1, m=None, density=None, seed=None, max_rhs=4, tnzcols=None, route="chol", mix=None):
     """a measured case: pattern, parts of dense_ref.measure ('scaling': cholesky_projected_inverse in one call, with and without
     the separator factors), right-hand sides of the Hessians, and the KKT input (m, density, seed: dense_ref's recipe unless
-    given; max_rhs also sizes the context)"""
-    kkt = dict(m=m, density=density, seed=seed, max_rhs=max_rhs, tnzcols=tnzcols, route=route)
+    given; max_rhs also sizes the context; mix: the order of a mixed recipe, dense_ref.interleave -- m counts its wide
+    constraints, which tnzcols must send through the Hessian and the others to the SCMcolumn2 columns: the hybrid Schur route)"""
+    kkt = dict(m=m, density=density, seed=seed, max_rhs=max_rhs, tnzcols=tnzcols, route=route, mix=mix)
     return ("case", pattern, tuple(parts), nrhs, kkt)
 
 
@@ -177,6 +185,32 @@ ZSP_CASE = C("dense450", ("kkt",), m=5, density=0.01, seed=42, max_rhs=3, tnzcol
 DYN_CASE = C("tops8", ("kkt",), m=40, density=0.004, seed=5, max_rhs=40, tnzcols=0.0)
 SHARED_CASE = C("fam_shared", ("kkt",), m=13, density=0.003, seed=73, max_rhs=13, tnzcols=0.0)
 GRAM130 = C("nested", ("kkt",), m=130, density=0.05, seed=9)      # more than one 128-block of constraints: k_gram_partial
+# the thin last round of the fused extend-add (k_lf_zero_pairs behind SMCP_FZ_TAIL) and the pairs shared from the start
+# (tail_first = 0: it does not depend on that switch); entries per constraint within 4 * nsn, so that the extend-add stays fused
+TAIL_CASE = C("tail8", ("kkt",), m=40, density=0.002, seed=33, max_rhs=40, tnzcols=0.0)
+PAIRS_CASE = C("fan32", ("kkt",), m=20, density=0.004, seed=62, max_rhs=20, tnzcols=0.0)
+
+
+def hybrid(case, tnzcols):
+    """the hybrid variant of a sparse-input case: its constraints as the wide class (same m, density, seed, max_rhs: within
+    cnnz <= 4 * nsn * m and m <= max_rhs, so the entry-driven family kernels and the fused extend-add stay live, now reading the
+    swept subset through kc_ids), 4 few + 3 single dealt among them; the KKT part alone"""
+    k = case[4]
+    return C(case[1], ("kkt",), m=k["m"], density=k["density"], seed=k["seed"], max_rhs=k["max_rhs"], tnzcols=tnzcols,
+             mix=dense_ref.interleave(k["m"], 4, 3))
+
+
+# tnzcols: int(n * tnzcols) lies between the 6 rows / columns a narrow constraint touches at most and what the wide ones touch
+# (test_hybrid_recipes.py holds that on a CPU for every case; the device's classification is asserted where the case runs)
+FAM_HYBRID = [hybrid(FAM_SPARSE[0], 0.1), hybrid(FAM_SPARSE[1], 0.1)]
+FZ_HYBRID = hybrid(FZ_CASE, 0.1)
+THIN_HYBRID = hybrid(THIN_CASE, 0.1)
+LFSP_HYBRID = hybrid(LFSP_CASE, 0.1)
+DYN_HYBRID = hybrid(DYN_CASE, 0.1)
+SHARED_HYBRID = hybrid(SHARED_CASE, 0.1)
+PAIRS_HYBRID = hybrid(PAIRS_CASE, 0.1)
+NESTED_HYBRID = C("nested", ("kkt",), m=5, density=0.05, seed=9, max_rhs=5, tnzcols=0.2, mix=dense_ref.interleave(5, 4, 3))
+HYBRIDS = [NESTED_HYBRID] + FAM_HYBRID + [FZ_HYBRID, THIN_HYBRID, LFSP_HYBRID, DYN_HYBRID, SHARED_HYBRID, PAIRS_HYBRID]
 EVERYTHING = [C("nested_mid", ALL), C("arrow_big", ALL), C("nested_mid", ("hessian",), nrhs=4)]
 
 
@@ -200,6 +234,10 @@ SCENARIOS = {
     "units_spectra": S({}, SPECTRA_UNITS),
     "units_factor": S({}, FACTOR_UNITS),
     "units_kkt": S({}, KKT_UNITS),
+    # the hybrid Schur route on the default routes: the Gram block of the swept subset scattered into H (k_scatter_hd) beside the
+    # SCMcolumn2 columns (k_unit_columns, k_scm_columns); the scenarios below run the same cases where a switch changes a kernel
+    # that reads the subset through kc_ids
+    "hybrid": S({}, HYBRIDS, ran_k=["k_scatter_hd", "k_scm_columns", "k_unit_columns"]),
 }
 
 
@@ -228,35 +266,40 @@ _add("flow0", {"SMCP_FLOW": "0"}, [C("band275", ALL), C("three_tops", ("tree", "
 _add("flow_wg5", {"SMCP_FLOW_WG": "5"}, [C("band275", ("tree", "scaling")), C("three_tops", ("tree", "scaling"))],
      note="not observable: the same kernel on fewer workgroups")
 _N16 = [C("nested", ("hessian", "kkt")), C("fam_odd", ("hessian", "kkt")), C("nested", ("hessian",), nrhs=4), C("fam_odd", ("hessian",), nrhs=4)]
-_add("n16_0", {"SMCP_N16": "0"}, _N16, gone=["k_hess_up_n16"], note="k_hess_up_pad runs on both routes (fam_odd's shapes beyond n16)")
+_add("n16_0", {"SMCP_N16": "0"}, _N16 + FAM_HYBRID, gone=["k_hess_up_n16"], note="k_hess_up_pad runs on both routes (fam_odd's shapes beyond n16)")
 _add("oldlds1", {"SMCP_OLDLDS": "1"}, _N16, ran=["k_hess_up_mfma<true>"], gone=["k_hess_up_n16", "k_hess_up_pad"])
 _add("down_w0", {"SMCP_DOWN_W": "0"}, _N16, gone_k=["k_hess_down_w<*"],
      note="the id k_hess_down_mfma<true> holds k_hess_down_w<1..4> and k_hess_down_mfma<true, *>: only the census shows the switch")
 _add("fam0", {"SMCP_FAM": "0"}, [C(name, ("scaling", "hessian", "kkt"), nrhs=nrhs) for name in ("fam_odd", "fam_max", "fam_nine") for nrhs in (1, 4)],
      gone=["k_hess_up_fam", "k_hess_up_fam1", "k_hess_down_fam", "k_fam_terms", "k_famt_prep", "k_chol_fam", "k_pinv_fam", "k_leaf_*"])
-_add("fam2_0", {"SMCP_FAM2": "0"}, FAM_SPARSE, tune={"LEAFGRAM": 2}, ran=["k_hess_up_fam"], gone=["k_fam_terms", "k_famt_prep"],
+_add("fam2_0", {"SMCP_FAM2": "0"}, FAM_SPARSE + FAM_HYBRID, tune={"LEAFGRAM": 2}, ran=["k_hess_up_fam"], gone=["k_fam_terms", "k_famt_prep"],
      note="k_fam_sparse runs on neither route here: the default is the entry-driven k_fam_terms")
-_add("famt0", {"SMCP_FAMT": "0"}, FAM_SPARSE, tune={"LEAFGRAM": 2}, ran=["k_fam_sparse", "k_fam2_prep"], gone=["k_fam_terms", "k_famt_prep"])
-_add("leafgram0", {"SMCP_LEAFGRAM": "0"}, FAM_SPARSE, tune={"LEAFGRAM": 2}, ran=["k_fam_sparse"], gone=["k_leaf_pairs", "k_leaf_tables", "k_fam_terms"])
-_add("famt_group0", {"SMCP_FAMT_GROUP": "0"}, [SHARED_CASE], ran=["k_fam_terms"], gone=["k_fam_terms_grp"])
-_add("fz0", {"SMCP_FZ": "0"}, [FZ_CASE], tune={"LEAFGRAM": 2}, ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_fz"])
-_add("lfsp0", {"SMCP_LFSP": "0"}, [THIN_CASE, LFSP_CASE], gone=["k_lfsp_up", "k_lfsp_prep"])
+_add("famt0", {"SMCP_FAMT": "0"}, FAM_SPARSE + FAM_HYBRID, tune={"LEAFGRAM": 2}, ran=["k_fam_sparse", "k_fam2_prep"], gone=["k_fam_terms", "k_famt_prep"])
+_add("leafgram0", {"SMCP_LEAFGRAM": "0"}, FAM_SPARSE + FAM_HYBRID, tune={"LEAFGRAM": 2}, ran=["k_fam_sparse"], gone=["k_leaf_pairs", "k_leaf_tables", "k_fam_terms"])
+_add("famt_group0", {"SMCP_FAMT_GROUP": "0"}, [SHARED_CASE, SHARED_HYBRID], ran=["k_fam_terms"], gone=["k_fam_terms_grp"])
+_add("fz0", {"SMCP_FZ": "0"}, [FZ_CASE, FZ_HYBRID, PAIRS_CASE, PAIRS_HYBRID], tune={"LEAFGRAM": 2}, ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_fz"],
+     gone_k=["k_lf_zero_pairs"],
+     note="k_lf_zero_pairs clears the update blocks of the pairs whose children the fused extend-add deals over several workgroups: on fan32 "
+          "every pair from the start (alds_route: nz = 2), whatever SMCP_FZ_TAIL says")
+_add("lfsp0", {"SMCP_LFSP": "0"}, [THIN_CASE, LFSP_CASE, THIN_HYBRID, LFSP_HYBRID], gone=["k_lfsp_up", "k_lfsp_prep"])
 _add("zsp0", {"SMCP_ZSP": "0"}, [ZSP_CASE], ran=["k_scatter_constraints"], gone=["k_lf_zsp"])
 _add("gram0", {"SMCP_GRAM": "0"}, [C("nested", ("kkt",)), C("arrow", ("kkt",)), C("nested_mid", ("kkt",)), GRAM130], gone=["k_gram_*"])
-_add("scm0", {"SMCP_SCM": "0"}, [C("rand2", ("kkt",)), C("arrow", ("kkt",)), C("nested_mid", ("kkt",), tnzcols=0.2)],
-     note="not observable: the SCMcolumn2 route is host-side bookkeeping over the same kernels")
+_add("scm0", {"SMCP_SCM": "0"}, [C("rand2", ("kkt",)), C("arrow", ("kkt",)), C("nested_mid", ("kkt",), tnzcols=0.2), NESTED_HYBRID, FAM_HYBRID[0]],
+     gone_k=["k_scm_columns", "k_unit_columns", "k_scatter_hd"],
+     note="the switch turns the column-sparse class off: every constraint is swept, the hybrid cases run as plain Gram sweeps")
 _add("trsm_mm0", {"SMCP_TRSM_MM": "0"}, [C("arrow_big", ("trsm",)), C("nested_mid", ("trsm",))], gone=["k_lf_prep_k", "k_prep_lk"],
      gone_k=["k_trsm_mm_fwd", "k_trsm_mm_bwd"],
      note="the ids show the inverse-form factor the tile products need (k_prep_lk, k_lf_prep_k), the census the tile products themselves, "
           "which run under the ids of the level kernels; k_trsm_*_level run on both routes (blocks of fewer than eight columns)")
-_add("alds0", {"SMCP_ALDS": "0"}, [FAN_CASE, THIN_CASE, DYN_CASE], gone=["k_lf_assemble_lds", "k_lf_assemble_lds_dyn"],
+_add("alds0", {"SMCP_ALDS": "0"}, [FAN_CASE, THIN_CASE, DYN_CASE, THIN_HYBRID, DYN_HYBRID], gone=["k_lf_assemble_lds", "k_lf_assemble_lds_dyn"],
      note="k_lf_assemble (the gather plan) runs on both routes: the levels below 32 pairs")
 _add("alds_dyn0", {"SMCP_ALDS_DYN": "0"}, [DYN_CASE], ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_lds_dyn"])
-_add("alds_fill0", {"SMCP_ALDS_FILL": "0"}, [FZ_CASE, THIN_CASE], tune={"LEAFGRAM": 2}, ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_fz"], sig_over=1)
+_add("alds_fill0", {"SMCP_ALDS_FILL": "0"}, [FZ_CASE, FZ_HYBRID, THIN_CASE, THIN_HYBRID], tune={"LEAFGRAM": 2}, ran=["k_lf_assemble_lds"], gone=["k_lf_assemble_fz"], sig_over=2)
 _add("asm_t", {"SMCP_ASM": "t"}, [C("arrow_big", ("hessian",), nrhs=2), THIN_CASE, C("arrow_big", ("kkt",))], ran=["k_lf_clear_upd"], ran_k=["k_lf_assemble_tiled"],
      note="the id k_lf_assemble holds the tiled kernel and the gather plan: the ids show the clear pass the tiled kernel needs, the census the kernel")
-_add("fz_tail0", {"SMCP_FZ_TAIL": "0"}, [FZ_CASE, FAN_CASE], tune={"LEAFGRAM": 2}, note="not observable on these cases: the same k_lf_assemble_fz launch without shares in its last round; the shares would show as k_lf_zero_pairs, "
-          "which neither case reaches (EXEMPT_KERNELS: no last round less than half full over fronts of sixteen children)")
+_add("fz_tail0", {"SMCP_FZ_TAIL": "0"}, [TAIL_CASE, FZ_CASE, FAN_CASE], tune={"LEAFGRAM": 2}, gone_k=["k_lf_zero_pairs"],
+     note="the same k_lf_assemble_fz launch without shares in its last round: the shares show as k_lf_zero_pairs, the clear pass of the shared pairs. "
+          "tail8 reaches them (40 queues of pairs on 32 queues of workgroups); nested_mid and fan40 do not and are there for their numerics")
 _add("faci_lds0", {"SMCP_FACI_LDS": "0"}, [C("nested", ("hessian", "kkt")), C("fam_max", ("hessian", "kkt"))], ran=["k_factor_inverse"], gone=["k_factor_inverse_lds"])
 _SCALING = [C("nested_mid", ("scaling", "hessian", "kkt")), C("fam_odd", ("scaling", "hessian", "kkt"))]
 _add("chol_prep0", {"SMCP_CHOL_PREP": "0"}, [C("nested_mid", ("scaling",)), C("tops8", ("scaling",)), C("fan40", ("scaling",))] + _SCALING,
@@ -313,13 +356,10 @@ EXEMPT_KERNELS = {
     "k_stack_rows": "kkt.hip kkt_stack_rows: the top of the tree sharded by constraint, more than one rank",
     "k_lf_root1": "capi.hip hess_up_fast: SMCP_ROOT_FUSED=1, a study switch (EXEMPT_SWITCHES: the condition number squared)",
     "k_lf_root2": "capi.hip hess_down_fast: SMCP_ROOT_FUSED=1, a study switch (EXEMPT_SWITCHES: the condition number squared)",
-    "k_scatter_hd": "kkt.hip kkt_schur_gram_part: the hybrid Schur route, dense-on-V and column-sparse constraints in ONE system; "
-                    "checked on one rank only as the reference of test_column_sparse_constraints_sharded_by_constraint",
-    "k_scatter_constraints_ids": "kkt.hip kkt_schur_gram_part: the hybrid Schur route (as k_scatter_hd) without the entry lists of the sparse-input sweep",
-    "k_lf_zero_pairs": "capi.hip launch_assemble_fz: a last round less than half full of more than 256 (front, right-hand side) pairs whose fronts "
-                       "have sixteen children or more, or a sharded sweep; the cases of fz_tail0 do not reach it",
+    "k_scatter_constraints_ids": "kkt.hip schur_gram: the hybrid Schur route when the entry tables of the sparse-input sweep are absent, which "
+                                 "constraints.cpp decides: nsn * (m + 1) > 2^28 or nnz >= 2^31; no test of seconds reaches either",
 }
-MAX_EXEMPT_KERNELS = 8
+MAX_EXEMPT_KERNELS = 6
 # kernels (ids or functions) that no input reaches: kernel -> the launch site
 DEAD_KERNELS = {
     "k_selftest_mma": "front_mfma.hip: the self-test of the MFMA operand map has no launch site in the library",
@@ -406,9 +446,21 @@ def _context(pattern, max_rhs):
     return _CTX[key]
 
 
+def recipe_of(kkt):
+    """(m, density, seed) or, mixed, (m, density, seed, mix) of a case's KKT input"""
+    recipe = (kkt["m"] or dense_ref.KKT_M, kkt["density"] or dense_ref.KKT_DENSITY, kkt["seed"] or dense_ref.KKT_SEED)
+    return recipe + (kkt["mix"],) if kkt.get("mix") else recipe
+
+
+def classes_of(kkt):
+    """(swept, sparse) a hybrid case must be classified as; None for a plain recipe"""
+    mix = kkt.get("mix")
+    return (mix.count("w"), len(mix) - mix.count("w")) if mix else None
+
+
 def set_recipe(case, kkt):
     """the KKT input of a case: dense_ref's recipe unless the case names its own"""
-    recipe = (kkt["m"] or dense_ref.KKT_M, kkt["density"] or dense_ref.KKT_DENSITY, kkt["seed"] or dense_ref.KKT_SEED)
+    recipe = recipe_of(kkt)
     if case.kkt_recipe != recipe:
         case.kkt_recipe, case._kkt = recipe, None
 
@@ -430,6 +482,9 @@ def run_measured(case_, tune):
     from tests.helpers import kernel_census, launch_counts
     _, pattern, parts, nrhs, kkt = case_
     symb, case = _context(pattern, max(4, kkt["max_rhs"], nrhs))
+    classes = classes_of(kkt)
+    if classes and os.environ.get("SMCP_SCM") == "0":              # the switch that turns the sparse class off: every constraint swept
+        classes = (sum(classes), 0)
     kernels = _SETUP.pop((pattern, max(4, kkt["max_rhs"], nrhs)), {})
     set_recipe(case, kkt)
     errs = {}
@@ -439,7 +494,7 @@ def run_measured(case_, tune):
             errs[op] = max(errs.get(op, 0.0), float(e))
 
     def run():
-        ops = dense_ref.device_ops(symb, case, route=kkt["route"], tnzcols=kkt["tnzcols"], max_rhs=kkt["max_rhs"])
+        ops = dense_ref.device_ops(symb, case, route=kkt["route"], tnzcols=kkt["tnzcols"], max_rhs=kkt["max_rhs"], classes=classes)
         if "scaling" in parts:
             merge(_scaling_errors(symb, case))
         merge(dense_ref.measure(case, ops, nrhs=nrhs, parts=tuple(p for p in parts if p != "scaling")))
@@ -619,7 +674,7 @@ def signature_faults(counts, ran, gone):
 
 
 def error_faults(results, cases, bound_of):
-    """cases that failed, did not run, or exceed bound_of(pattern, operation)"""
+    """cases that failed, did not run, or exceed bound_of(case, operation)"""
     bad = []
     for case_ in cases:
         key = case_key(case_)
@@ -630,7 +685,7 @@ def error_faults(results, cases, bound_of):
             bad.append("%s: %s" % (key, r["failed"]))
         else:
             for op, e in sorted(r["errors"].items()):
-                b = bound_of(case_[1], op)
+                b = bound_of(case_, op)
                 if not e <= b:
                     bad.append("%s: %s %.2e > %.2e" % (key, op, e, b))
     return bad
@@ -642,9 +697,21 @@ def recipes_of(pattern):
     for scn in SCENARIOS.values():
         for c in scn["cases"]:
             if c[0] == "case" and c[1] == pattern and "kkt" in c[2]:
-                r = (c[4]["m"] or out[0][0], c[4]["density"] or out[0][1], c[4]["seed"] or out[0][2])
+                r = recipe_of(c[4])
                 if r not in out:
                     out.append(r)
+    return out
+
+
+def hybrid_cases():
+    """the hybrid cases of the scenarios in the form of dense_ref.HYBRID_CASES, once each: recipe key -> case"""
+    out = {}
+    for scn in SCENARIOS.values():
+        for c in scn["cases"]:
+            if c[0] == "case" and c[4].get("mix"):
+                k = c[4]
+                hc = dense_ref.hybrid_case(c[1], k["m"], k["density"], k["seed"], k["mix"], k["tnzcols"], max_rhs=k["max_rhs"])
+                out[dense_ref.recipe_key(c[1], hc["recipe"])] = hc
     return out
 
 
@@ -668,11 +735,16 @@ def load_ledger_yardstick():
         return json.load(f)
 
 
-def bound_of(pattern, op, yard=None, own=None):
+def bound_of(case, op, yard=None, own=None, mixed=None):
     """dense_ref.device_bound(op); for a NEW pattern whose recorded oracle-vs-dense error is beyond the yardstick of
-    GPU_PATTERNS, 100 x its own recorded value; never looser than dense_ref.BOUND_CAP"""
+    GPU_PATTERNS, 100 x its own recorded value (over every recipe the ledger uses on it, the mixed ones included); for a mixed
+    recipe on a pattern of GPU_PATTERNS the same rule on the record of that recipe (dense_ref.hybrid_bound); never looser
+    than dense_ref.BOUND_CAP.  case: a case of a scenario, or a pattern name"""
     yard = dense_ref.load_yardstick() if yard is None else yard
+    pattern = case if isinstance(case, str) else case[1]
     b = dense_ref.device_bound(op, yard)
+    if not isinstance(case, str) and case[0] == "case" and case[4].get("mix") and pattern not in NEW_PATTERNS and op.startswith("kkt_"):
+        return dense_ref.hybrid_bound(dense_ref.recipe_key(pattern, recipe_of(case[4])), op, yard, mixed)
     if pattern in NEW_PATTERNS:
         own = load_ledger_yardstick() if own is None else own
         v = float(own[pattern].get(op, 0.0))

@@ -4,9 +4,11 @@ smcp_amd/csrc/switches.hpp is shown taking effect by one -- or is listed with th
 
 Per scenario: every error against the dense definitions is at most dense_ref.device_bound (for a pattern outside GPU_PATTERNS
 whose recorded oracle-vs-dense error is beyond the yardstick: 100 x its own recorded value, capped at 1e-12 -- fan40: dot, llt;
-tops8: kkt_H, kkt_y, logdiagsum; route_ledger.bound_of), the units pass their own checks, the signature holds on the scenario's
-routes and the opposite signature on the default routes.  No other tolerance; signatures are counts of zero or at least one, over
-the kernel ids (csp_profile_*: `ran`, `gone`) and over the kernel functions (csp_census_*: `ran_k`, `gone_k`).
+tops8: kkt_H, kkt_y, logdiagsum; tail8: dot, hessian, hessian_gadj_g, kkt_x, llt; fan32: llt; for a mixed KKT recipe on a pattern
+of GPU_PATTERNS the same rule on the record of that recipe, tests/golden/hybrid_recipe_yardstick.json; route_ledger.bound_of),
+the units pass their own checks, the signature holds on the scenario's routes and the opposite signature on the default routes.
+No other tolerance; signatures are counts of zero or at least one, over the kernel ids (csp_profile_*: `ran`, `gone`) and over
+the kernel functions (csp_census_*: `ran_k`, `gone_k`).
 
 What is counted.  A kernel id stands for a group of kernels (KID_ceig: k_ceig, k_ceig_vec, k_cone_split and the fifteen kernels
 of the chip-wide block Jacobi; KID_hess_down_mfma<true>: k_hess_down_mfma<true, *> and k_hess_down_w<1..4>; ...).  The launch
@@ -21,9 +23,9 @@ products (MUST_BE_LAUNCHED).  To refresh it, run the ledger, read the line "LEDG
 MEASURED on one MI355X in one run (another run or machine will differ in the last digits and in the times):
 
     kernel ids                142, every one launched by a passing scenario
-    kernel functions          209: 197 launched by a passing scenario, 8 exempt (EXEMPT_KERNELS), 2 without a launch site
+    kernel functions          209: 199 launched by a passing scenario, 6 exempt (EXEMPT_KERNELS), 2 without a launch site
                               (DEAD_KERNELS: k_selftest_mma, k_exchange_copy), 2 not counted (NOT_COUNTED)
-    kernel instantiations     399: 284 launched by a passing scenario, 101 recorded in kernel_census.json, 14 of the exempt,
+    kernel instantiations     399: 288 launched by a passing scenario, 99 recorded in kernel_census.json, 12 of the exempt,
                               dead and uncounted functions
     before this file counted functions, with the census alone added to the scenarios it had then: 158 functions and 240
     instantiations were launched by a passing scenario
@@ -31,9 +33,11 @@ MEASURED on one MI355X in one run (another run or machine will differ in the las
 What the census found when it was added: the 40 kernels of clique_eigh .. clique_decompose ran in no scenario (now: units_spectra,
 units_factor); the column block of 2 .. 4 columns of k_trmm_n, k_trmm_t and k_symm_fma ran in no unit (now: 3 columns in `trmm` and
 `symm`); k_dense_trsv_step, k_stack_gemm_panel, k_qr_shift, k_latch_status, k_res_combine_cliques, k_diag_fingerprint and
-k_fingerprint_compare ran in no scenario (now: units_kkt, generic, verify_cache); fz_tail0 never reaches the shares it switches
-off (k_lf_zero_pairs, exempt with its condition) and the hybrid Schur route (k_scatter_hd) is checked on one rank only as the
-reference of a sharded test (exempt with its condition); two kernels have no launch site at all.
+k_fingerprint_compare ran in no scenario (now: units_kkt, generic, verify_cache); fz_tail0 never reached the shares it switches
+off (k_lf_zero_pairs) and the hybrid Schur route (k_scatter_hd) was checked on one rank only as the reference of a sharded
+test; two kernels have no launch site at all.  Since then: hybrid variants of the sparse-input cases -- the
+swept constraints a non-contiguous subset, read through kc_ids -- run on the default routes (`hybrid`) and under every switch
+that changes a kernel reading the subset; tail8 and fan32 reach k_lf_zero_pairs, so fz_tail0, fz0 and scm0 have signatures.
 
 Worst device-vs-dense error per operation over the scenarios' own routes, against the bound in force for its pattern:
 
@@ -47,8 +51,8 @@ Worst device-vs-dense error per operation over the scenarios' own routes, agains
     hessian_gadj_g        1.6e-15        2.0e-13    default_small (dense600)
     hessian_gram          6.2e-16        4.4e-14    large0 (arrow_big)
     hessian_inv           2.3e-15        2.6e-13    default_small (rand2)
-    kkt_H                 5.9e-16        2.3e-13    qr_trsm_f (nested)
-    kkt_x                 1.9e-15        2.0e-13    default_small (nested)
+    kkt_H                 9.2e-16        2.4e-13    hybrid (tops8)
+    kkt_x                 2.0e-15        2.1e-13    fz_tail0 (tail8)
     kkt_y                 2.0e-15        4.9e-13    zsp0 (dense450)
     llt                   2.1e-16        1.8e-14    default_small (rand1)
     logdiagsum            1.9e-16        1.7e-13    trtri0 (two_fronts)
@@ -59,52 +63,56 @@ Per scenario: wall time (child interpreter: start, import and context set-up inc
 error closest to its bound over both runs (the scenario's routes and the default routes of the same cases):
 
     scenario          switches                                      time    where    operation          error    bound
-    alds0             ALDS=0                                         4.9 s child    kkt_x              1.4e-15  2.0e-13
-    alds_dyn0         ALDS_DYN=0                                     4.1 s child    kkt_x              1.2e-15  2.0e-13
-    alds_fill0        ALDS_FILL=0                                    4.1 s child    kkt_x              1.4e-15  2.0e-13
-    asm_t             ASM=t                                          2.9 s child    hessian_gram       2.9e-16  4.4e-14
-    chol_prep0        CHOL_PREP=0                                    3.1 s child    projected_inverse  9.5e-16  8.4e-14
-    default_small     (default routes)                               0.5 s in-proc  llt                2.1e-16  1.8e-14
-    down_w0           DOWN_W=0                                       2.5 s child    hessian            1.4e-15  1.9e-13
-    fac_partial0      FAC_PARTIAL=0                                  2.8 s child    projected_inverse  8.2e-16  8.4e-14
-    faci_lds0         FACI_LDS=0                                     2.5 s child    hessian_gram       2.9e-16  4.4e-14
-    fam0              FAM=0                                          2.9 s child    projected_inverse  6.7e-16  8.4e-14
-    fam2_0            FAM2=0                                         2.8 s child    kkt_x              1.4e-15  2.0e-13
-    famt0             FAMT=0                                         2.8 s child    kkt_x              1.4e-15  2.0e-13
-    famt_group0       FAMT_GROUP=0                                   2.7 s child    kkt_x              1.1e-15  2.0e-13
-    flow0             FLOW=0                                         2.7 s child    projected_inverse  8.5e-16  8.4e-14
-    flow_wg5          FLOW_WG=5                                      2.6 s child    projected_inverse  8.5e-16  8.4e-14
-    fz0               FZ=0                                           3.7 s child    kkt_x              1.4e-15  2.0e-13
-    fz_tail0          FZ_TAIL=0                                      4.6 s child    kkt_x              1.4e-15  2.0e-13
-    generic           GENERIC=1                                      2.6 s child    hessian_adjoint    5.8e-17  6.9e-15
-    gram0             GRAM=0                                         2.8 s child    kkt_x              1.9e-15  2.0e-13
-    gram_side         GRAM_EARLY=1 LG_SIDE=0                         4.0 s child    hessian_gram       6.1e-16  4.4e-14
-    large0            LARGE=0                                        3.1 s child    hessian_gram       6.2e-16  4.4e-14
-    leafgram0         LEAFGRAM=0                                     2.9 s child    kkt_x              1.4e-15  2.0e-13
-    lfsp0             LFSP=0                                         3.0 s child    hessian_gram       2.9e-16  4.4e-14
-    lg_early0         LG_EARLY=0                                     4.1 s child    hessian_gram       6.1e-16  4.4e-14
-    mid0              MID=0                                          2.9 s child    projected_inverse  7.9e-16  8.4e-14
-    n16_0             N16=0                                          2.6 s child    hessian            1.4e-15  1.9e-13
-    oldlds1           OLDLDS=1                                       2.5 s child    hessian            1.4e-15  1.9e-13
-    pd1               PD=1                                           3.7 s child    hessian_gram       6.1e-16  4.4e-14
-    products_mm0      TRMM_MM=0 SYR2K_MM=0 SYMM_MM=0 LOWRANK_MM=0    3.8 s child    -                  0.0e+00  0.0e+00
-    products_mm2      TRMM_MM=2 SYR2K_MM=2 SYMM_MM=2                 2.8 s child    -                  0.0e+00  0.0e+00
-    qr_trsm_f         QR_TRSM=f                                      2.7 s child    kkt_x              1.3e-15  2.0e-13
-    scaling_overlap0  SCALING_OVERLAP=0                              2.8 s child    projected_inverse  8.3e-16  8.4e-14
-    scm0              SCM=0                                          2.9 s child    kkt_x              1.6e-15  2.0e-13
-    streams           FORK=0 NOCACHE=1 POTRF_DEFER=0                 3.5 s child    hessian_gram       6.1e-16  4.4e-14
-    trsm_mm0          TRSM_MM=0                                      2.6 s child    trsm               6.1e-16  8.6e-14
-    trtri0            TRTRI=0                                        2.6 s child    projected_inverse  6.0e-16  8.4e-14
-    units             (default routes)                               5.7 s child    kkt_x              9.6e-16  2.0e-13
-    units_factor      (default routes)                               2.9 s child    -                  0.0e+00  0.0e+00
-    units_kkt         (default routes)                               5.4 s child    -                  0.0e+00  0.0e+00
-    units_spectra     (default routes)                               5.2 s child    -                  0.0e+00  0.0e+00
-    verify_cache      tune VERIFY_CACHE=1                            0.8 s in-proc  hessian_gram       6.1e-16  4.4e-14
-    zsp0              ZSP=0                                          2.5 s child    kkt_x              1.4e-15  2.0e-13
+    alds0             ALDS=0                                          7.1 s child    kkt_x              1.4e-15  2.0e-13
+    alds_dyn0         ALDS_DYN=0                                      4.1 s child    kkt_x              1.2e-15  2.0e-13
+    alds_fill0        ALDS_FILL=0                                     5.7 s child    kkt_x              1.4e-15  2.0e-13
+    asm_t             ASM=t                                           3.1 s child    hessian_gram       2.9e-16  4.4e-14
+    chol_prep0        CHOL_PREP=0                                     3.4 s child    projected_inverse  9.5e-16  8.4e-14
+    default_small     (default routes)                                0.5 s in-proc  llt                2.1e-16  1.8e-14
+    down_w0           DOWN_W=0                                        3.3 s child    hessian            1.4e-15  1.9e-13
+    fac_partial0      FAC_PARTIAL=0                                   3.2 s child    projected_inverse  8.3e-16  8.4e-14
+    faci_lds0         FACI_LDS=0                                      2.8 s child    hessian_gram       2.9e-16  4.4e-14
+    fam0              FAM=0                                           3.0 s child    projected_inverse  6.7e-16  8.4e-14
+    fam2_0            FAM2=0                                          3.6 s child    kkt_x              1.4e-15  2.0e-13
+    famt0             FAMT=0                                          3.4 s child    kkt_x              1.4e-15  2.0e-13
+    famt_group0       FAMT_GROUP=0                                    2.7 s child    kkt_x              1.3e-15  2.0e-13
+    flow0             FLOW=0                                          2.8 s child    projected_inverse  8.5e-16  8.4e-14
+    flow_wg5          FLOW_WG=5                                       2.5 s child    projected_inverse  8.5e-16  8.4e-14
+    fz0               FZ=0                                            5.6 s child    kkt_x              1.6e-15  2.0e-13
+    fz_tail0          FZ_TAIL=0                                       7.5 s child    kkt_x              2.0e-15  2.1e-13
+    generic           GENERIC=1                                       2.8 s child    hessian_adjoint    5.8e-17  6.9e-15
+    gram0             GRAM=0                                          2.9 s child    kkt_x              1.7e-15  2.0e-13
+    gram_side         GRAM_EARLY=1 LG_SIDE=0                          4.0 s child    hessian_gram       6.1e-16  4.4e-14
+    hybrid            (default routes)                                0.5 s in-proc  kkt_x              1.4e-15  2.0e-13
+    large0            LARGE=0                                         3.3 s child    hessian_gram       6.2e-16  4.4e-14
+    leafgram0         LEAFGRAM=0                                      3.5 s child    kkt_x              1.4e-15  2.0e-13
+    lfsp0             LFSP=0                                          4.0 s child    hessian_gram       2.9e-16  4.4e-14
+    lg_early0         LG_EARLY=0                                      4.1 s child    hessian_gram       6.1e-16  4.4e-14
+    mid0              MID=0                                           2.8 s child    projected_inverse  7.9e-16  8.4e-14
+    n16_0             N16=0                                           3.3 s child    hessian            1.4e-15  1.9e-13
+    oldlds1           OLDLDS=1                                        2.5 s child    hessian            1.4e-15  1.9e-13
+    pd1               PD=1                                            3.5 s child    hessian_gram       6.1e-16  4.4e-14
+    products_mm0      TRMM_MM=0 SYR2K_MM=0 SYMM_MM=0 LOWRANK_MM=0     3.7 s child    -                  0.0e+00  0.0e+00
+    products_mm2      TRMM_MM=2 SYR2K_MM=2 SYMM_MM=2                  2.7 s child    -                  0.0e+00  0.0e+00
+    qr_trsm_f         QR_TRSM=f                                       2.7 s child    kkt_x              1.3e-15  2.0e-13
+    scaling_overlap0  SCALING_OVERLAP=0                               3.0 s child    projected_inverse  8.3e-16  8.4e-14
+    scm0              SCM=0                                           3.3 s child    kkt_x              1.6e-15  2.0e-13
+    streams           FORK=0 NOCACHE=1 POTRF_DEFER=0                  3.4 s child    hessian_gram       6.1e-16  4.4e-14
+    trsm_mm0          TRSM_MM=0                                       2.6 s child    trsm               6.1e-16  8.6e-14
+    trtri0            TRTRI=0                                         2.5 s child    projected_inverse  6.0e-16  8.4e-14
+    units             (default routes)                                5.2 s child    kkt_x              9.6e-16  2.0e-13
+    units_factor      (default routes)                                3.0 s child    -                  0.0e+00  0.0e+00
+    units_kkt         (default routes)                                5.1 s child    -                  0.0e+00  0.0e+00
+    units_spectra     (default routes)                                5.0 s child    -                  0.0e+00  0.0e+00
+    verify_cache      tune VERIFY_CACHE=1                             0.7 s in-proc  hessian_gram       6.1e-16  4.4e-14
+    zsp0              ZSP=0                                           2.6 s child    kkt_x              1.4e-15  2.0e-13
 
 The units of `units`, `units_spectra`, `units_factor`, `units_kkt`, `products_mm0`, `products_mm2`, and the units inside `generic`
 and `flow0`, assert inside their own modules (no figure here).  No bound was exceeded and no signature failed; every one of the
-142 kernel ids was launched by a passing scenario.  The whole ledger took 136 s.
+142 kernel ids was launched by a passing scenario.  The whole ledger took 164 s; as the fixture of this module inside the whole suite 165 s,
+against 147 s before the hybrid cases, tail8 and fan32 were added.  The largest single item is tail8, about 6 s (its dense reference
+of order 1374 is formed in the child of fz_tail0 and again in this process); the hybrid variants add 0.5 .. 2 s to each of the
+scenarios they entered (alds0 4.9 -> 7.1 s, fz0 3.7 -> 5.6 s, alds_fill0 4.1 -> 5.7 s, fz_tail0 4.6 -> 7.5 s).
 """
 import os
 import tempfile
@@ -118,14 +126,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # measured wall time of every child, seconds (same run as the table above); a child's timeout is ten times that, rounded up, and
 # at least 120 s: a limit that ends trouble, not a performance claim
-CHILD_SECONDS = {"alds0": 4.9, "alds_dyn0": 4.1, "alds_fill0": 4.1, "asm_t": 2.9, "chol_prep0": 3.1,
-                 "down_w0": 2.5, "fac_partial0": 2.8, "faci_lds0": 2.5, "fam0": 2.9, "fam2_0": 2.8,
-                 "famt0": 2.8, "famt_group0": 2.7, "flow0": 2.7, "flow_wg5": 2.6, "fz0": 3.7,
-                 "fz_tail0": 4.6, "generic": 2.6, "gram0": 2.8, "gram_side": 4.0, "large0": 3.1,
-                 "leafgram0": 2.9, "lfsp0": 3.0, "lg_early0": 4.1, "mid0": 2.9, "n16_0": 2.6,
-                 "oldlds1": 2.5, "pd1": 3.7, "products_mm0": 3.8, "products_mm2": 2.8, "qr_trsm_f": 2.7,
-                 "scaling_overlap0": 2.8, "scm0": 2.9, "streams": 3.5, "trsm_mm0": 2.6, "trtri0": 2.6,
-                 "units": 5.7, "units_factor": 2.9, "units_kkt": 5.4, "units_spectra": 5.2, "zsp0": 2.5}
+CHILD_SECONDS = {"alds0": 7.1, "alds_dyn0": 4.1, "alds_fill0": 5.7, "asm_t": 3.1, "chol_prep0": 3.4, "down_w0": 3.3,
+                 "fac_partial0": 3.2, "faci_lds0": 2.8, "fam0": 3.0, "fam2_0": 3.6, "famt0": 3.4, "famt_group0": 2.7,
+                 "flow0": 2.8, "flow_wg5": 2.5, "fz0": 5.6, "fz_tail0": 7.5, "generic": 2.8, "gram0": 2.9,
+                 "gram_side": 4.0, "large0": 3.3, "leafgram0": 3.5, "lfsp0": 4.0, "lg_early0": 4.1, "mid0": 2.8,
+                 "n16_0": 3.3, "oldlds1": 2.5, "pd1": 3.5, "products_mm0": 3.7, "products_mm2": 2.7, "qr_trsm_f": 2.7,
+                 "scaling_overlap0": 3.0, "scm0": 3.3, "streams": 3.4, "trsm_mm0": 2.6, "trtri0": 2.5, "units": 5.2,
+                 "units_factor": 3.0, "units_kkt": 5.1, "units_spectra": 5.0, "zsp0": 2.6}
 
 
 # kernels of which tests/golden/kernel_census.json may hold no instantiation: everything added since the ledger, and the arms of
@@ -161,7 +168,7 @@ def test_every_route_switch_is_in_the_ledger():
 
 
 def test_exempt_and_dead_kernel_lists_are_within_their_caps():
-    assert len(rl.EXEMPT_KERNELS) <= rl.MAX_EXEMPT_KERNELS == 8
+    assert len(rl.EXEMPT_KERNELS) <= rl.MAX_EXEMPT_KERNELS == 6
     assert not set(rl.EXEMPT_KERNELS) & set(rl.DEAD_KERNELS)
     assert all(isinstance(r, str) and len(r) > 20 for r in list(rl.EXEMPT_KERNELS.values()) + list(rl.DEAD_KERNELS.values()))
     assert len(rl.NOT_COUNTED) <= rl.MAX_NOT_COUNTED == 4
@@ -267,8 +274,8 @@ def scenario_faults(name, rec):
         return [rec["skipped"]]
     if rec["run"] is None or rec["rc"] not in (0, 1):
         return ["child ended with %s: %s" % (rec["rc"], rec["tail"])]
-    yard, own = dense_ref.load_yardstick(), rl.load_ledger_yardstick()
-    bound = lambda pattern, op: rl.bound_of(pattern, op, yard, own)
+    yard, own, mixed = dense_ref.load_yardstick(), rl.load_ledger_yardstick(), dense_ref.load_mix_yardstick()
+    bound = lambda case, op: rl.bound_of(case, op, yard, own, mixed)
     bad = rl.error_faults(rec["run"], scn["cases"], bound)
     judged = [rl.case_key(c) for c in scn["cases"][:scn["sig_over"]]]
     if not bad:
